@@ -10,11 +10,15 @@ B = 65536 chasers per GPU (weak scaling over GPUs: shards of independent chasers
 in the timed region).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--nx 40 --dv]
+    python bench.py --full           (the headline + the CPU baseline + the four legs, see below)
+    python bench.py --dump-outputs DIR   (what the last timed step computed, as DIR/<name>.npy)
     python bench.py --continuous     (BASELINE config 4: trajectorySimulateC's loop, see below)
     (--gpus N > 1 without torchrun: relaunched under torch.distributed.run, one rank per GPU)
 
 Rank 0 prints one JSON line: metric/value/... + roofline (graded on the LDS, the resource the
-solve steps run on; HBM and FP64 fractions beside it) + cold (single-shot) rate + cpu_baseline
+solve steps run on; HBM and FP64 fractions beside it, all from the timed steps' own counts) + cold
+(single-shot) rate.  A plain run does nothing else: set-up, warm-up, the timed steps, the outputs
+if asked for, the line.  With --full the line also carries cpu_baseline
 + four legs measured in the same run, each with its own roofline: config3 (N = 40 impulsive
 delta-v, BASELINE config 3) and n40_accel (N = 40 continuous acceleration, the horizon of every
 reference script), both at the headline's window, config2 (BASELINE config 2: B = 1,024 at N = 20,
@@ -233,6 +237,7 @@ def closed_loop_run(prob, X0, B, K, W, S, eps, rank, device, dist=None, track=No
     rhou = torch.zeros(K, B, dtype=torch.int32, device=device)
     stat = torch.zeros(K, B, dtype=torch.int32, device=device)
     act = torch.zeros(K, B, dtype=torch.bool, device=device)
+    last = [None] * S
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -249,18 +254,67 @@ def closed_loop_run(prob, X0, B, K, W, S, eps, rank, device, dist=None, track=No
                 iters[k, cut[j]:cut[j + 1]].copy_(r.iter, non_blocking=True)
                 rhou[k, cut[j]:cut[j + 1]].copy_(r.rho_updates, non_blocking=True)
                 stat[k, cut[j]:cut[j + 1]].copy_(r.status, non_blocking=True)
-            c.step_after_solve(r)
+            last[j] = c.step_after_solve(r)
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     kt = np.array([[a.elapsed_time(b) for a, b in ev[j]] for j in range(S)]) * 1e-3
     kt_cold = np.array([a.elapsed_time(b) for a, b in cold_ev]) * 1e-3
-    return dict(cls=cls, cut=cut, elapsed=elapsed, kt=kt, kt_cold=kt_cold, cold_wall=cold_wall,
+    return dict(cls=cls, cut=cut, last=last, elapsed=elapsed, kt=kt, kt_cold=kt_cold,
+                cold_wall=cold_wall,
                 it=iters.cpu().numpy(), ru=rhou.cpu().numpy(), st=stat.cpu().numpy(),
                 act=act.cpu().numpy(), cold_it=cold_it.cpu().numpy(),
                 cold_act=cold_act.cpu().numpy(), dims=cls[0].qp.dims(),
                 sched=cls[0].qp.schedule_info())
+
+
+DUMP_ROWS = 4096            # chasers whose whole primal / dual solution is written
+DUMP_FULL_BATCH = 1 << 16   # up to here the per-chaser figures are written for every chaser
+
+
+def save_finite(path, name, a, mask=False):
+    """<path>/<name>.npy in float64 with finite entries only, so that the difference of two dumps is
+    a number everywhere: a NaN (what the engine hands back for an instance without a solution, as
+    OSQP's store_solution does, and the run summary for a chaser that never solved) is written as
+    0 and an infinite objective as the largest double of its sign; mask=True also writes
+    <name>_nan.npy, 1 where the NaNs were."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if mask:
+        np.save(os.path.join(path, f"{name}_nan.npy"), np.isnan(a).astype(np.float64))
+    np.save(os.path.join(path, f"{name}.npy"), np.nan_to_num(a, nan=0.0))
+
+
+def dump_outputs(path, parts, results, seed, rank=0, world=1):
+    """--dump-outputs: what the timed path handed back in its last timed step, one float64 .npy per
+    array under `path` (two builds run with the same arguments write comparable files: the inputs
+    are seeded).  parts: the loop's shards in chaser order, results: each shard's last SolveResult.
+    Per chaser: the solve's status, ADMM iterations, objective and residuals, then the loop's state
+    after that step (applied control, true and estimated state, termination flag, controller
+    index).  The primal and dual solutions are written for a fixed sample of DUMP_ROWS chasers
+    (drawn from the seed, rows.npy; every chaser when the batch is smaller), and beyond
+    DUMP_FULL_BATCH chasers the per-chaser arrays are cut to the same sample, which keeps the files
+    below 64 MB in all.  The files hold finite numbers (save_finite)."""
+    import torch
+
+    for c in parts:
+        c.qp.stream.synchronize()
+    B = sum(c.B for c in parts)
+    rows = np.sort(np.random.default_rng(seed).choice(B, size=min(B, DUMP_ROWS), replace=False))
+    dev_rows = torch.as_tensor(rows, device=parts[0].device)
+    small = slice(None) if B <= DUMP_FULL_BATCH else dev_rows
+    arrays = {"rows": rows}
+    for name in ("x", "y"):
+        arrays[f"solve_{name}"] = torch.cat([getattr(r, name) for r in results])[dev_rows]
+    for name in ("status", "iter", "obj_val", "pri_res", "dua_res"):
+        arrays[f"solve_{name}"] = torch.cat([getattr(r, name) for r in results])[small]
+    for name in ("ctrl", "x_true", "xest", "done", "ctrl_seq"):
+        arrays[name] = torch.cat([getattr(c, name) for c in parts])[small]
+    os.makedirs(path, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        save_finite(path, name + tag, a.cpu().numpy() if isinstance(a, torch.Tensor) else a,
+                    mask=name == "solve_x")
 
 
 def roofline(run, S, K, elapsed):
@@ -367,6 +421,8 @@ def bench_discrete(args, rank, world, device, dist):
     import torch
 
     summ = _launch.gather_rows(torch.cat([c.summary() for c in cls]), world * B, rank, world, dist)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, cls, run["last"], args.seed, rank, world)
     solved = float(run["act"].sum())
     if dist:
         t = torch.tensor([elapsed, solved], dtype=torch.float64, device=device)
@@ -436,7 +492,11 @@ def bench_discrete(args, rank, world, device, dist):
     }
     for c in cls:
         c.close()
-    if world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs:  # the gathered run summaries (rank 0 holds every rank's rows)
+        keep = Sn if Sn.shape[0] <= DUMP_FULL_BATCH else Sn[np.sort(np.random.default_rng(
+            args.seed).choice(Sn.shape[0], size=DUMP_ROWS, replace=False))]
+        save_finite(args.dump_outputs, "summary", keep, mask=True)
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             # every core this process may run on: the affinity mask, capped by the cgroup CPU
             # quota when one is set (the GPU box grants 16 CPUs of a 256-thread host: 256 threads
@@ -572,6 +632,8 @@ def bench_continuous(args, rank, world, device, dist):
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, parts, rs, args.seed, rank, world)
     a = act.cpu().numpy()
     it = iters.cpu().numpy()
     solved = float(a.sum())
@@ -640,19 +702,29 @@ def main(argv=None):
     ap.add_argument("--cpu-sample", type=int, default=16384)
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="oracle threads (default: every core in this process's affinity mask)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the CPU baseline (the oracle on a sample "
+                         "of the same QPs, with its agreement figures) and the legs: N=40 delta-v "
+                         "(config 3), N=40 continuous acceleration, B=1,024 (config 2) and the "
+                         "continuous-time loop (config 4).  Off by default: a plain run sets up, "
+                         "warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (solve results and "
+                         "loop state per chaser, float64) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--cont-split", type=int, default=3,
                     help="concurrent HIP-stream shards of the continuous-time loop (config 4; "
                          "measured 183.5k / 192.2k / 194.1k solves/s with 1 / 2 / 3)")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the N=40 legs (config 3 delta-v, N=40 continuous acceleration, "
-                         "config 4 continuous-time loop) of the default run")
+                    help="with --full: skip the legs (config 3 delta-v, N=40 continuous "
+                         "acceleration, config 2, config 4 continuous-time loop)")
     ap.add_argument("--leg-steps", type=int, default=0,
                     help="timed steps of the N=40 discrete legs (default: --steps)")
     ap.add_argument("--leg-warmup", type=int, default=None,
                     help="untimed steps of the N=40 discrete legs (default: --warmup)")
     ap.add_argument("--cont-steps", type=int, default=5,
-                    help="timed sample periods of the config-4 leg of the default run")
+                    help="timed sample periods of the config-4 leg of a --full run")
     ap.add_argument("--continuous", action="store_true",
                     help="BASELINE config 4: the continuous-time nonlinear loop (default N=40)")
     ap.add_argument("--order", choices=("iters", "none"), default="none",
@@ -675,7 +747,7 @@ def main(argv=None):
     else:
         out = bench_discrete(args, rank, world, device, dist)
         default_cfg = (args.nx, args.dv) == (20, False)
-        if out is not None and world == 1 and default_cfg and not args.no_legs:
+        if args.full and out is not None and world == 1 and default_cfg and not args.no_legs:
             for key, nx, dv in (("config3", 40, True), ("n40_accel", 40, False)):
                 try:
                     out[key] = bench_leg(args, rank, device, nx, dv)
@@ -689,6 +761,7 @@ def main(argv=None):
             try:
                 ca = argparse.Namespace(**vars(args))
                 ca.nx, ca.dv, ca.steps, ca.warmup = 40, False, args.cont_steps, 1
+                ca.dump_outputs = None  # the outputs written are the headline's
                 out["config4"] = bench_continuous(ca, rank, world, device, dist)
             except Exception as e:  # report, never fake
                 out["config4"] = {"error": repr(e)}

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Profile evidence at HEAD (GPU box): default bench with the CPU baseline; rocprofv3 kernel trace of
+# Profile evidence at HEAD (on the GPU): the full bench (--full: CPU baseline, legs); rocprofv3 kernel trace of
 # the default workload; PMC passes (FETCH_SIZE / WRITE_SIZE with calibration, SQ LDS counters); the
 # N=40 impulsive delta-v bench (BASELINE config 3) with its kernel trace; the continuous-time loop
 # (config 4) with its kernel trace.   usage: tools/profile.sh <tag>
@@ -7,7 +7,7 @@ set -o pipefail
 R="$GRAFT_REPO_ROOT"; O="$R/gpurun_out/${1:-prof}"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 B="python3 $R/bench.py --no-cpu-baseline --no-legs"
-timeout -k 10 400 python3 $R/bench.py > "$O/bench.json" 2> "$O/bench.err" || { echo bench failed; tail -5 "$O/bench.err"; exit 1; }
+timeout -k 10 400 python3 $R/bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { echo bench failed; tail -5 "$O/bench.err"; exit 1; }
 echo "bench: $(head -c 300 $O/bench.json)"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -o run -- $B > "$O/trace_bench.json" 2> "$O/trace.err" || { echo trace failed; tail -5 "$O/trace.err"; exit 1; }
 echo trace ok
