@@ -104,9 +104,10 @@ class BatchClosedLoop:
         self.qp.set_data(q=prob.q, Ax=Ax, l=l, u=u)
         f = dict(dtype=torch.float64, device=self.device)
         self.x_true = torch.as_tensor(x0, **f).contiguous()
+        # not swapped for in-track runs: the reference's initial configureDynamicConstraints call
+        # swaps a temporary (quirk Q4 reaches xestO from the first step on), so the first
+        # controller select reads the plain [x0, 0, 0] (src/trajectorySimulate.py:234,249,300)
         self.xest = torch.as_tensor(xest, **f).contiguous()
-        if prob.inTrack:  # quirk Q4 applied by the initial configureDynamicConstraints call
-            self.xest[:, [0, 1]] = self.xest[:, [1, 0]]
         self.ctrl_prev = torch.zeros(self.B, 2, **f)
         self.ctrl = torch.zeros(self.B, 2, **f)
         self.xintf = torch.zeros(self.B, **f)
@@ -431,8 +432,6 @@ class BatchClosedLoopC(BatchClosedLoop):
         check(_lib.lib().mpcqp_cl_set_ids(self._cl, int(id_offset)), "mpcqp_cl_set_ids")
         self.iterm = torch.full((self.B,), self.nsimC, dtype=torch.int32, device=self.device)
         xest = self.xest.cpu().numpy()
-        if prob.inTrack:
-            xest[:, [0, 1]] = xest[:, [1, 0]]
         hold = int(prob.T / self.T_cont)
         self._init_noise(noise, noise_seed, noise_source, xest, noise_dt=prob.T * hold)
         self.period_index = 0
