@@ -25,8 +25,11 @@
  *   mpcqp_destroy                  <- object destruction  [osqp_cleanup]
  *
  * Differences from OSQP by design: one handle holds a BATCH of B independent QPs that share the
- * sparsity pattern of P and A (and the values of P and q); A values and the bounds l, u are per
- * instance.  B = 1 is the reference's use.
+ * sparsity pattern of P and A; A values and the bounds l, u are per instance.  The cost data (the
+ * values of P, and q) are shared by the batch with mpcqp_set_data / mpcqp_update_lin_cost /
+ * mpcqp_update_P and per instance with their _batched forms (e.g. one weight set per instance of a
+ * tuning sweep); each P_i must be positive semidefinite, which is not checked.  B = 1 is the
+ * reference's use.
  *
  * Rules
  *   - every function returns 0 on success and a negative MPCQP_E* code on failure; nothing throws
@@ -105,10 +108,15 @@ int mpcqp_create(const mpcqp_structure *st, const mpcqp_settings *s, int32_t bat
                  mpcqp_handle **out);
 int mpcqp_destroy(mpcqp_handle *h);
 
-/* Problem data (device): Px [nnzP] and q [n] shared by all instances; Ax [B*nnzA] (CSC order),
- * l, u [B*m].  Resets the warm-start state of every instance (cold start, rho = settings.rho). */
+/* Problem data (device): Px [nnzP] and q [n] shared by all instances (mpcqp_set_data_batched: per
+ * instance); Ax [B*nnzA] (CSC order), l, u [B*m].  Resets the warm-start state of every instance (cold start, rho = settings.rho). */
 int mpcqp_set_data(mpcqp_handle *h, const double *Px, const double *q, const double *Ax,
                    const double *l, const double *u);
+/* mpcqp_set_data with per-instance cost data: Px [B*nnzP], q [B*n] (device, row per instance).
+ * The handle keeps a set-up row per instance from here on (allocated at the first batched call);
+ * a later plain mpcqp_set_data returns it to one shared row. */
+int mpcqp_set_data_batched(mpcqp_handle *h, const double *Px, const double *q, const double *Ax,
+                           const double *l, const double *u);
 /* New bounds for every instance [B*m] (device).  Alone (no mpcqp_update_A before the next solve)
  * this is osqp_update_bounds: the instance keeps its data scaling D, E, c -- the next solve re-runs
  * the Ruiz passes on the same unscaled data as the last scaling did, bitwise the same factors --
@@ -116,10 +124,23 @@ int mpcqp_set_data(mpcqp_handle *h, const double *Px, const double *q, const dou
 int mpcqp_update_bounds(mpcqp_handle *h, const double *l, const double *u);
 /* New A values for every instance [B*nnzA] (device, CSC order): osqp_update_A.  The next solve of
  * each instance unscales its last scaled data (P, q, and the bounds as mpcqp_update_bounds scaled
- * them by the previous E), overwrites A and re-runs the Ruiz scaling -- OSQP 0.6's data drift. */
+ * them by the previous E), overwrites A and re-runs the Ruiz scaling -- OSQP 0.6's data drift.
+ * When the bounds change as well, call mpcqp_update_bounds first (the reference's per-step pair):
+ * the rescaling treats the bounds it finds as scaled by the previous E, whatever the call order. */
 int mpcqp_update_A(mpcqp_handle *h, const double *Ax);
 /* New shared linear cost q [n] (device). */
 int mpcqp_update_lin_cost(mpcqp_handle *h, const double *q);
+/* mpcqp_update_lin_cost with a q per instance [B*n] (device). */
+int mpcqp_update_lin_cost_batched(mpcqp_handle *h, const double *q);
+/* New P values (device, upper-triangular CSC order), shared [nnzP] or per instance [B*nnzP]:
+ * osqp_update_P.  The next solve of each instance unscales its last scaled data, takes the new P in
+ * place of the unscaled one and re-runs the Ruiz scaling, as after mpcqp_update_A (iterates and rho
+ * are kept); an instance that was never solved simply gets the new set-up values.  When the bounds
+ * change as well, call mpcqp_update_bounds first (OSQP's Python update() applies l / u before Px /
+ * Ax too): the rescaling passes the bounds it finds through E_old, E_old^-1, E_new.  The batched
+ * form moves a handle with shared cost data to per-instance set-up rows. */
+int mpcqp_update_P(mpcqp_handle *h, const double *Px);
+int mpcqp_update_P_batched(mpcqp_handle *h, const double *Px);
 /* Warm start every instance from unscaled primal/dual guesses x [B*n], y [B*m] (device). */
 int mpcqp_warm_start(mpcqp_handle *h, const double *x, const double *y);
 

@@ -83,6 +83,10 @@ int mpcqp_cl_set_tracking(mpcqp_cl *cl, int32_t *iterm, int32_t *success, double
 
 /* Global id of instance 0 of this handle (a rank's shard offset); keys the noise streams. */
 int mpcqp_cl_set_ids(mpcqp_cl *cl, int64_t id0);
+/* period > 0: the noise stream of instance b is keyed by (id0 + b) % period instead of id0 + b, so
+ * the blocks of `period` consecutive global ids (e.g. one block per cost-weight set of a sweep) draw
+ * the same noise realisations (common random numbers); 0 restores the default. */
+int mpcqp_cl_set_id_period(mpcqp_cl *cl, int64_t period);
 
 /* noise [B*4] = [sig_x g0, sig_y g1, 0, 0], g ~ N(0, 1) from Philox-4x32-10 with key seed and
  * counter (draw, global id): draw k of chaser id is the same in every sharding. */

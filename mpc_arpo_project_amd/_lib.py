@@ -49,6 +49,8 @@ EXPORTED = (
     "mpcqp_emu_solve",
     "mpcqp_status_string", "mpcqp_last_error", "mpcqp_version", "mpcqp_engine_kind", "mpcqp_schedule_kind",
     "mpcqp_kernel_info",
+    "mpcqp_set_data_batched", "mpcqp_update_lin_cost_batched", "mpcqp_update_P",
+    "mpcqp_update_P_batched", "mpcqp_cl_set_id_period",
     "mpcqp_cl_create", "mpcqp_cl_destroy", "mpcqp_cl_configure", "mpcqp_cl_step",
     "mpcqp_cl_set_ids", "mpcqp_cl_set_tracking", "mpcqp_cl_noise", "mpcqp_cl_set_plant", "mpcqp_clc_period",
     "mpcqp_ukf_create", "mpcqp_ukf_destroy", "mpcqp_ukf_step", "mpcqp_plant_rk45",
@@ -152,9 +154,13 @@ def lib():
                                C.POINTER(vp)])
     _sig(L, "mpcqp_destroy", "argtypes", [vp])
     _sig(L, "mpcqp_set_data", "argtypes", [vp, dp, dp, dp, dp, dp])
+    _sig(L, "mpcqp_set_data_batched", "argtypes", [vp, dp, dp, dp, dp, dp])
     _sig(L, "mpcqp_update_bounds", "argtypes", [vp, dp, dp])
     _sig(L, "mpcqp_update_A", "argtypes", [vp, dp])
     _sig(L, "mpcqp_update_lin_cost", "argtypes", [vp, dp])
+    _sig(L, "mpcqp_update_lin_cost_batched", "argtypes", [vp, dp])
+    _sig(L, "mpcqp_update_P", "argtypes", [vp, dp])
+    _sig(L, "mpcqp_update_P_batched", "argtypes", [vp, dp])
     _sig(L, "mpcqp_warm_start", "argtypes", [vp, dp, dp])
     _sig(L, "mpcqp_solve", "argtypes", [vp, dp, dp, C.POINTER(Info)])
     _sig(L, "mpcqp_dims", "argtypes", [vp, i32p, i32p, i32p, i32p, i32p])
@@ -183,6 +189,7 @@ def lib():
     _sig(L, "mpcqp_cl_configure", "argtypes", [vp, dp, dp, dp, dp])
     _sig(L, "mpcqp_cl_step", "argtypes", [vp, dp, dp, i32, i32, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp])
     _sig(L, "mpcqp_cl_set_ids", "argtypes", [vp, C.c_int64])
+    _sig(L, "mpcqp_cl_set_id_period", "argtypes", [vp, C.c_int64])
     _sig(L, "mpcqp_cl_set_tracking", "argtypes", [vp, dp, dp, dp, dp, C.c_double, C.c_double])
     _sig(L, "mpcqp_cl_noise", "argtypes", [vp, C.c_uint64, C.c_uint64, C.c_double, C.c_double, dp])
     _sig(L, "mpcqp_cl_set_plant", "argtypes", [vp, C.POINTER(PlantModel), i32])

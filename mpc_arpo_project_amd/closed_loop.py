@@ -25,7 +25,7 @@ import torch
 from . import _lib
 from ._lib import MPCQPError, check
 from .engine import BatchQP, data_buffers
-from .qp_model import MPCProblem, configure_batch
+from .qp_model import MPCProblem, configure_batch, cost_variants
 
 
 def scenario_struct(prob: MPCProblem):
@@ -87,21 +87,36 @@ class BatchClosedLoop:
     stream keyed by (noise_seed, global chaser id = id_offset + b, draw index); a callable
     draw(k) -> (B, 4) array supplies draw k from the host instead (e.g. numpy's seeded global
     generator, for parity with the reference's own runs).
+
+    prob may be a list of problems that differ only in their cost weights
+    (qp_model.cost_variants checks it) with variant, an int array [B]: chaser b runs the weight
+    set probs[variant[b]] -- its P, q and constant A values; everything else is the family's and
+    runs through the one closed-loop handle.  id_period: mpcqp_cl_set_id_period (chasers whose
+    global ids are a period apart draw the same device noise).
     """
 
-    def __init__(self, prob: MPCProblem, x0, device="cuda", noise=None, noise_seed=123,
-                 id_offset=0, noise_source=None, longest_first=False, **settings):
+    def __init__(self, prob, x0, device="cuda", noise=None, noise_seed=123,
+                 id_offset=0, noise_source=None, longest_first=False, variant=None, id_period=0,
+                 **settings):
         x0 = np.asarray(x0, dtype=float)
         if x0.ndim != 2 or x0.shape[1] != 4:
             raise ValueError("x0 must have shape (B, 4)")
+        probs = None
+        if isinstance(prob, (list, tuple)):
+            probs, prob = list(prob), prob[0]
+        elif variant is not None:
+            raise ValueError("variant needs a list of problems")
         self.prob = prob
         self.B = x0.shape[0]
         settings.setdefault("warm_start", True)
         self.qp = BatchQP(prob.P, prob.A, batch=self.B, device=device, **settings)
         self.device = self.qp.device
         xest = np.hstack([x0, np.zeros((self.B, 2))])  # xest0 = [x0, 0, 0] (src/...:249)
-        Ax, l, u = configure_batch(prob, xest)
-        self.qp.set_data(q=prob.q, Ax=Ax, l=l, u=u)
+        if probs is None:
+            Ax, l, u = configure_batch(prob, xest)
+            self.qp.set_data(q=prob.q, Ax=Ax, l=l, u=u)
+        else:
+            self.variant = self._set_variant_data(probs, variant, xest)
         f = dict(dtype=torch.float64, device=self.device)
         self.x_true = torch.as_tensor(x0, **f).contiguous()
         # not swapped for in-track runs: the reference's initial configureDynamicConstraints call
@@ -140,7 +155,28 @@ class BatchClosedLoop:
         self.u0 = prob.u0_slice.start
         self.steps = 0
         check(_lib.lib().mpcqp_cl_set_ids(self._cl, int(id_offset)), "mpcqp_cl_set_ids")
+        if id_period:
+            check(_lib.lib().mpcqp_cl_set_id_period(self._cl, int(id_period)),
+                  "mpcqp_cl_set_id_period")
         self._init_noise(noise, noise_seed, noise_source, xest, noise_dt=None)
+
+    def _set_variant_data(self, probs, variant, xest):
+        """set_data for a mix of weight sets: P and q per instance, gathered by variant; the
+        initial Ax, l, u from configure_batch of each chaser's own problem"""
+        variant = np.zeros(self.B, dtype=np.int64) if variant is None else np.asarray(variant)
+        if variant.shape != (self.B,) or not np.issubdtype(variant.dtype, np.integer):
+            raise ValueError(f"variant must be an int array of shape ({self.B},)")
+        if variant.size and (variant.min() < 0 or variant.max() >= len(probs)):
+            raise ValueError("variant must index the list of problems")
+        Px, q, _ = cost_variants(probs)
+        Ax = np.empty((self.B, self.prob.nnzA))
+        l = np.empty((self.B, self.prob.m))
+        u = np.empty((self.B, self.prob.m))
+        for v in np.unique(variant):
+            rows = np.flatnonzero(variant == v)
+            Ax[rows], l[rows], u[rows] = configure_batch(probs[v], xest[rows])
+        self.qp.set_data(Px=Px[variant], q=q[variant], Ax=Ax, l=l, u=u)
+        return variant
 
     def _init_noise(self, noise, seed, source, xest0, noise_dt):
         self.noise = _noise_params(noise)
@@ -312,14 +348,22 @@ class ShardedClosedLoop:
     the unsharded loop: chasers are independent and keep their global ids (noise streams).
     """
 
-    def __init__(self, prob: MPCProblem, x0, shards=2, device="cuda", id_offset=0,
-                 noise_source=None, **kw):
+    def __init__(self, prob, x0, shards=2, device="cuda", id_offset=0,
+                 noise_source=None, variant=None, **kw):
         x0 = np.asarray(x0, dtype=float)
         B = x0.shape[0]
         S = max(1, min(int(shards), B))
         self.cut = [B * j // S for j in range(S + 1)]
         dev = torch.device(device)
         self.parts = []
+        if variant is not None:  # a list of problems: each shard takes its chasers' weight sets
+            variant = np.asarray(variant)
+            if variant.shape != (B,):
+                raise ValueError(f"variant must be an int array of shape ({B},)")
+
+        def shard_variant(j):
+            return {} if variant is None else dict(variant=variant[self.cut[j]:self.cut[j + 1]])
+
         # a host noise source draws for the WHOLE batch (e.g. numpy's seeded global generator):
         # draw k once, cache it, hand each shard its rows, so the host RNG advances exactly as in
         # the unsharded loop
@@ -340,7 +384,8 @@ class ShardedClosedLoop:
         for j in range(S):
             self.parts.append(BatchClosedLoop(prob, x0[self.cut[j]:self.cut[j + 1]], device=dev,
                                               id_offset=id_offset + self.cut[j], stream=sts[j],
-                                              noise_source=shard_source(j), **kw))
+                                              noise_source=shard_source(j), **shard_variant(j),
+                                              **kw))
         torch.cuda.synchronize(dev)
 
     def step(self):

@@ -261,11 +261,12 @@ __device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t 
 // (src/trajectorySimulate.py:268,352-353), from a counter-based stream keyed by the global chaser
 // id, so that a chaser's noise does not depend on how the batch is sharded
 __global__ void __launch_bounds__(256) cl_noise_kernel(int B, uint64_t seed, int64_t id0,
-                                                       uint64_t draw, double sx, double sy,
-                                                       double* noise) {
+                                                       int64_t period, uint64_t draw, double sx,
+                                                       double sy, double* noise) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  const uint64_t id = (uint64_t)(id0 + b);
+  // period > 0: ids a period apart share their stream (mpcqp_cl_set_id_period)
+  const uint64_t id = (uint64_t)(period > 0 ? (id0 + b) % period : id0 + b);
   uint32_t c[4] = {(uint32_t)draw, (uint32_t)(draw >> 32), (uint32_t)id, (uint32_t)(id >> 32)};
   philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
   double g[4];
@@ -367,6 +368,7 @@ struct mpcqp_cl {
   int32_t* dpos = nullptr;
   hipStream_t stream = nullptr;
   int64_t id0 = 0;          // global id of instance 0 (noise streams)
+  int64_t id_period = 0;    // > 0: streams keyed by the global id modulo it (mpcqp_cl_set_id_period)
   bool has_plant = false;   // continuous-time plant set (mpcqp_cl_set_plant)
   PlantConsts pc{};
   int isDeltaV = 0;
@@ -452,12 +454,18 @@ int mpcqp_cl_set_ids(mpcqp_cl* cl, int64_t id0) {
   return 0;
 }
 
+int mpcqp_cl_set_id_period(mpcqp_cl* cl, int64_t period) {
+  if (!cl || period < 0) return -1;
+  cl->id_period = period;
+  return 0;
+}
+
 int mpcqp_cl_noise(mpcqp_cl* cl, uint64_t seed, uint64_t draw, double sig_x, double sig_y,
                    double* noise) {
   if (!cl || !noise) return -1;
   const int B = cl->d.B;
   hipLaunchKernelGGL(cl_noise_kernel, dim3((B + 255) / 256), dim3(256), 0, cl->stream, B, seed,
-                     cl->id0, draw, sig_x, sig_y, noise);
+                     cl->id0, cl->id_period, draw, sig_x, sig_y, noise);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -89,7 +89,10 @@ struct KParams {
   DevPlan pl;
   mpcqp_settings s;
   int B;
-  const double *Px, *q;      // shared
+  // set-up data: one row shared by every instance (stride 0) or a row per instance ([B][nnzP] /
+  // [B][n], strides nnzP / n: mpcqp_set_data_batched); setup_row
+  const double *Px, *q;
+  int Px_stride, q_stride;
   const double *Ax, *l, *u;  // [B][nnzA], [B][m]
   // warm-start state carried between solves (OSQP keeps it inside the workspace)
   double *xs, *zs, *ys, *rho_state, *Ecls;  // scaled iterates, rho, E of the previous scaling
@@ -106,7 +109,7 @@ struct KParams {
   // passes on that same input (bitwise the same D, E, c) -- while a solve after an update of A
   // (osqp_update_A) rescales the unscaled output.
   double *Pw, *qw;
-  int32_t* dsel;  // [B] -2 never scaled, -1 last scaled from the shared set-up data, 0 / 1 buffer
+  int32_t* dsel;  // [B] -2 never scaled, -1 last scaled from the set-up data, 0 / 1 buffer
   int32_t* pend;  // [B] A updated since the instance's last solve (mpcqp_update_A)
   int a_inplace;  // mpcqp_data_buffers handed out the A buffer: every solve follows an update of A
   double* scratch;  // [grid][nnzP + nnzA] scaled P and A values of the wave's current instance
@@ -126,7 +129,7 @@ struct KParams {
 // pointers at their two uses instead: measured per kernel, each form is 1.5-1.9 % faster in its own
 // kernel (register allocation).
 struct DriftSel {
-  int in_b, out_b;  // drift buffer the Ruiz passes scale (-1: the shared set-up data) / unscale into
+  int in_b, out_b;  // drift buffer the Ruiz passes scale (-1: the set-up data) / unscale into
   bool rebound;     // bounds through E_old, E_old^-1, E_new (osqp_update_A after update_bounds)
   int sel;          // dsel after this solve
 };
@@ -144,6 +147,11 @@ __device__ __forceinline__ DriftSel drift_sel(const KParams& p, int inst) {
   }
   return d;
 }
+// the set-up row of instance inst (KParams::Px / q with their stride; 0: the shared row).
+// Wave-uniform: scalar address arithmetic, the product in 64 bits
+__device__ __forceinline__ const double* setup_row(const double* base, int stride, int inst) {
+  return base + (size_t)inst * (size_t)stride;
+}
 // the drift buffers' rows of instance inst: P values (cnt = nnzP, base p.Pw) or q (n, p.qw)
 __device__ __forceinline__ double* drift_row(double* base, int b, int B, int cnt, int inst) {
   return base + ((size_t)b * B + inst) * cnt;
@@ -158,7 +166,7 @@ __device__ __forceinline__ Drift drift_of(const KParams& p, int inst) {
   const int nP = p.pl.nnzP, n = p.pl.n;
   const int sel = __builtin_amdgcn_readfirstlane(p.dsel[inst]);
   const bool dirty = p.a_inplace != 0 || __builtin_amdgcn_readfirstlane(p.pend[inst]) != 0;
-  int in_b, out_b;  // -1: the shared set-up data
+  int in_b, out_b;  // -1: the set-up data
   Drift d;
   if (sel == -2) {  // first solve after set_data: scale_data of the set-up data (osqp_setup)
     in_b = -1, out_b = 0, d.rebound = false, d.sel = -1;
@@ -169,8 +177,13 @@ __device__ __forceinline__ Drift drift_of(const KParams& p, int inst) {
     in_b = sel, out_b = sel == 0 ? 1 : 0, d.rebound = false, d.sel = sel;
   }
   const size_t BP = (size_t)p.B * nP, Bq = (size_t)p.B * n;
-  d.P_in = in_b < 0 ? p.Px : p.Pw + in_b * BP + (size_t)inst * nP;
-  d.q_in = in_b < 0 ? p.q : p.qw + in_b * Bq + (size_t)inst * n;
+  d.P_in = in_b < 0 ? setup_row(p.Px, p.Px_stride, inst) : p.Pw + in_b * BP + (size_t)inst * nP;
+  d.q_in = in_b < 0 ? setup_row(p.q, p.q_stride, inst) : p.qw + in_b * Bq + (size_t)inst * n;
+  // the two input rows are formed here, in scalar registers: left to sink the select and the
+  // set-up stride into scale_problem, the N = 20 kernel reloads one more spilled SGPR pair per ADMM
+  // iteration (tests/test_isa_hot_loops.py; with the pin its non-check iteration is 8
+  // instructions shorter than before the stride)
+  asm volatile("" : "+s"(d.P_in), "+s"(d.q_in));
   d.P_out = p.Pw + out_b * BP + (size_t)inst * nP;
   d.q_out = p.qw + out_b * Bq + (size_t)inst * n;
   return d;
@@ -2026,14 +2039,35 @@ __global__ void bcast_rows_kernel(double* dst, const double* src, int B, int cnt
 }
 
 // dst[b][k] = the unscaled data the instance's next update of A rescales (drift_of): buffer 1 - dsel
-// (dsel 0), buffer 0 (dsel -1 / 1), the shared set-up data (never scaled)
-__global__ void drift_gather_kernel(double* dst, const double* W, const double* shared,
+// (dsel 0), buffer 0 (dsel -1 / 1), the set-up data (never scaled; row stride 0 when shared)
+__global__ void drift_gather_kernel(double* dst, const double* W, const double* setup, int stride,
                                     const int32_t* dsel, int B, int cnt) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (size_t)B * cnt) return;
   const size_t b = t / (size_t)cnt, k = t % (size_t)cnt;
   const int sel = dsel[b];
-  dst[t] = sel == -2 ? shared[k] : W[(sel == 0 ? (size_t)B * cnt : 0) + t];
+  dst[t] = sel == -2 ? setup[b * (size_t)stride + k] : W[(sel == 0 ? (size_t)B * cnt : 0) + t];
+}
+
+// osqp_update_P: row b of src ([B][nnzP], or one row for every instance with src_stride 0) goes
+// where the instance's next solve finds its unscaled P (drift_of).  Never scaled (dsel -2): the
+// set-up row (with set-up stride 0 every such instance writes the one shared row, and only a
+// src_stride of 0 reaches this kernel then: the same values).  Otherwise the drift buffer that holds
+// the last solve's unscaled output -- buffer 1 (dsel 0) or 0 (dsel -1 / 1), what drift_gather_kernel
+// reports -- with pend = 1, so the next solve takes the osqp_update_A branch and rescales from it.
+__global__ void update_P_kernel(double* setup, int setup_stride, double* W, const double* src,
+                                int src_stride, const int32_t* dsel, int32_t* pend, int B, int cnt) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)B * cnt) return;
+  const size_t b = t / (size_t)cnt, k = t % (size_t)cnt;
+  const int sel = dsel[b];
+  const double val = src[b * (size_t)src_stride + k];
+  if (sel == -2) {
+    setup[b * (size_t)setup_stride + k] = val;
+  } else {
+    W[(sel == 0 ? (size_t)B * cnt : 0) + t] = val;
+    if (k == 0) pend[b] = 1;
+  }
 }
 
 // ---------------------------------------------------------------------------------------- host
@@ -2179,6 +2213,11 @@ struct mpcqp_handle {
   char* d_blob = nullptr;
   DevPlan dp{};
   double *Px = nullptr, *q = nullptr, *Ax = nullptr, *l = nullptr, *u = nullptr;
+  // per-instance set-up data [B][nnzP], [B][n]: allocated by the first batched call (batched_rows),
+  // in use while `batched` (from mpcqp_set_data_batched / a batched update to the next plain
+  // mpcqp_set_data)
+  double *PxB = nullptr, *qB = nullptr;
+  bool batched = false;
   double *xs = nullptr, *zs = nullptr, *ys = nullptr, *rho = nullptr, *Ecls = nullptr;
   double *Pw = nullptr, *qw = nullptr;  // OSQP's data drift (KParams::Pw): two buffers each
   int32_t *dsel = nullptr, *pend = nullptr;
@@ -2400,7 +2439,7 @@ int mpcqp_destroy(mpcqp_handle* h) {
   if (!h) return 0;
   void* bufs[] = {h->d_blob, h->Px, h->q,    h->Ax,        h->l,       h->u,      h->xs,
                   h->zs,     h->ys, h->Ecls, h->rho, h->has_state, h->scratch, h->counter,
-                  h->Pw,     h->qw, h->dsel, h->pend};
+                  h->Pw,     h->qw, h->dsel, h->pend, h->PxB, h->qB};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   delete h;
@@ -2431,6 +2470,43 @@ int mpcqp_set_data(mpcqp_handle* h, const double* Px, const double* q, const dou
   HIPCHK(hipMemsetD32Async(h->dsel, -2, B, h->stream));
   HIPCHK(hipMemsetAsync(h->pend, 0, sizeof(int32_t) * B, h->stream));
   h->has_data = true;
+  h->batched = false;  // the shared set-up row again (KParams stride 0)
+  return 0;
+}
+
+// the per-instance set-up buffers, allocated at the first batched call
+static int batched_rows(mpcqp_handle* h) {
+  const size_t B = (size_t)h->B;
+  if (!h->PxB) HIPCHK(hipMalloc(&h->PxB, sizeof(double) * B * std::max(1, h->plan.nnzP)));
+  if (!h->qB) HIPCHK(hipMalloc(&h->qB, sizeof(double) * B * h->plan.n));
+  return 0;
+}
+// a handle with shared set-up data moves to per-instance rows holding the same values
+static int promote(mpcqp_handle* h) {
+  if (h->batched) return 0;
+  if (int rc = batched_rows(h)) return rc;
+  HIPCHK(bcast_rows(h, h->PxB, h->Px, h->plan.nnzP));
+  HIPCHK(bcast_rows(h, h->qB, h->q, h->plan.n));
+  h->batched = true;
+  return 0;
+}
+
+int mpcqp_set_data_batched(mpcqp_handle* h, const double* Px, const double* q, const double* Ax,
+                           const double* l, const double* u) {
+  if (!h || !Px || !q || !Ax || !l || !u) return fail(MPCQP_E_INVALID, "null argument");
+  if (int rc = batched_rows(h)) return rc;
+  const Plan& pl = h->plan;
+  const size_t B = (size_t)h->B;
+  HIPCHK(hipMemcpyAsync(h->PxB, Px, sizeof(double) * B * pl.nnzP, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->qB, q, sizeof(double) * B * pl.n, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->Ax, Ax, sizeof(double) * B * pl.nnzA, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->l, l, sizeof(double) * B * pl.m, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->u, u, sizeof(double) * B * pl.m, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(h->has_state, 0, sizeof(int32_t) * B, h->stream));
+  HIPCHK(hipMemsetD32Async(h->dsel, -2, B, h->stream));
+  HIPCHK(hipMemsetAsync(h->pend, 0, sizeof(int32_t) * B, h->stream));
+  h->has_data = true;
+  h->batched = true;
   return 0;
 }
 
@@ -2457,11 +2533,50 @@ int mpcqp_update_lin_cost(mpcqp_handle* h, const double* q) {
   if (!h || !q) return fail(MPCQP_E_INVALID, "null argument");
   if (!h->has_data) return fail(MPCQP_E_NODATA, "update before set_data");
   HIPCHK(hipMemcpyAsync(h->q, q, sizeof(double) * h->plan.n, hipMemcpyDeviceToDevice, h->stream));
+  if (h->batched) HIPCHK(bcast_rows(h, h->qB, h->q, h->plan.n));
   // the next solve rescales the new q itself (OSQP would carry (q D) c unscaled: an ulp apart; the
   // reference never updates q): both drift buffers, whichever drift_of picks
   HIPCHK(bcast_rows(h, h->qw, h->q, h->plan.n));
   HIPCHK(bcast_rows(h, h->qw + (size_t)h->B * h->plan.n, h->q, h->plan.n));
   return 0;
+}
+
+int mpcqp_update_lin_cost_batched(mpcqp_handle* h, const double* q) {
+  if (!h || !q) return fail(MPCQP_E_INVALID, "null argument");
+  if (!h->has_data) return fail(MPCQP_E_NODATA, "update before set_data");
+  if (int rc = promote(h)) return rc;
+  // as mpcqp_update_lin_cost, row for row: the set-up q and both drift buffers
+  const size_t bytes = sizeof(double) * (size_t)h->B * h->plan.n;
+  HIPCHK(hipMemcpyAsync(h->qB, q, bytes, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->qw, q, bytes, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->qw + (size_t)h->B * h->plan.n, q, bytes, hipMemcpyDeviceToDevice,
+                        h->stream));
+  return 0;
+}
+
+// osqp_update_P for every instance (update_P_kernel): src_stride 0 = one row for all
+static int update_P(mpcqp_handle* h, const double* Px, int src_stride) {
+  const int cnt = h->plan.nnzP;
+  const size_t tot = (size_t)h->B * cnt;
+  if (tot == 0) return 0;
+  hipLaunchKernelGGL(update_P_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream,
+                     h->batched ? h->PxB : h->Px, h->batched ? cnt : 0, h->Pw, Px, src_stride,
+                     h->dsel, h->pend, h->B, cnt);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int mpcqp_update_P(mpcqp_handle* h, const double* Px) {
+  if (!h || !Px) return fail(MPCQP_E_INVALID, "null argument");
+  if (!h->has_data) return fail(MPCQP_E_NODATA, "update before set_data");
+  return update_P(h, Px, 0);
+}
+
+int mpcqp_update_P_batched(mpcqp_handle* h, const double* Px) {
+  if (!h || !Px) return fail(MPCQP_E_INVALID, "null argument");
+  if (!h->has_data) return fail(MPCQP_E_NODATA, "update before set_data");
+  if (int rc = promote(h)) return rc;
+  return update_P(h, Px, h->plan.nnzP);
 }
 
 int mpcqp_warm_start(mpcqp_handle* h, const double* x, const double* y) {
@@ -2486,7 +2601,9 @@ int mpcqp_solve(mpcqp_handle* h, double* x, double* y, const mpcqp_info* info) {
   p.pl = h->dp;
   p.s = h->set;
   p.B = h->B;
-  p.Px = h->Px, p.q = h->q, p.Ax = h->Ax, p.l = h->l, p.u = h->u;
+  p.Px = h->batched ? h->PxB : h->Px, p.q = h->batched ? h->qB : h->q;
+  p.Px_stride = h->batched ? h->plan.nnzP : 0, p.q_stride = h->batched ? h->plan.n : 0;
+  p.Ax = h->Ax, p.l = h->l, p.u = h->u;
   p.xs = h->xs, p.zs = h->zs, p.ys = h->ys, p.rho_state = h->rho, p.Ecls = h->Ecls;
   p.Pw = h->Pw, p.qw = h->qw;
   p.dsel = h->dsel, p.pend = h->pend, p.a_inplace = h->a_inplace ? 1 : 0;
@@ -2593,15 +2710,16 @@ int mpcqp_get_scaling(const mpcqp_handle* h, double* E, double* Pu, double* qu) 
   const size_t B = (size_t)h->B;
   const Plan& pl = h->plan;
   if (E) HIPCHK(hipMemcpyAsync(E, h->Ecls, sizeof(double) * B * pl.m, hipMemcpyDeviceToDevice, h->stream));
-  auto gather = [&](double* dst, const double* W, const double* shared, int cnt) {
+  // the set-up rows of a batched handle are per instance (KParams::Px_stride / q_stride)
+  auto gather = [&](double* dst, const double* W, const double* setup, int cnt) {
     const size_t tot = B * (size_t)cnt;
     if (tot == 0) return hipSuccess;
     hipLaunchKernelGGL(drift_gather_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
-                       h->stream, dst, W, shared, h->dsel, (int)B, cnt);
+                       h->stream, dst, W, setup, h->batched ? cnt : 0, h->dsel, (int)B, cnt);
     return hipGetLastError();
   };
-  if (Pu) HIPCHK(gather(Pu, h->Pw, h->Px, pl.nnzP));
-  if (qu) HIPCHK(gather(qu, h->qw, h->q, pl.n));
+  if (Pu) HIPCHK(gather(Pu, h->Pw, h->batched ? h->PxB : h->Px, pl.nnzP));
+  if (qu) HIPCHK(gather(qu, h->qw, h->batched ? h->qB : h->q, pl.n));
   return 0;
 }
 

@@ -429,8 +429,8 @@ __device__ __forceinline__ void scale_problem2(const KParams& p, int inst, const
   const DevPlan& P = p.pl;
   const int n = P.n, m = P.m, lane = W.lane, tid = lane + 64 * W.w;
   // OSQP's drifted P / q (drift_of, scale_problem of the one-wave kernel)
-  const double* P_in = dr.in_b < 0 ? p.Px : drift_row(p.Pw, dr.in_b, p.B, P.nnzP, inst);
-  const double* q_in = dr.in_b < 0 ? p.q : drift_row(p.qw, dr.in_b, p.B, n, inst);
+  const double* P_in = dr.in_b < 0 ? setup_row(p.Px, p.Px_stride, inst) : drift_row(p.Pw, dr.in_b, p.B, P.nnzP, inst);
+  const double* q_in = dr.in_b < 0 ? setup_row(p.q, p.q_stride, inst) : drift_row(p.qw, dr.in_b, p.B, n, inst);
   const double* Ax_in = p.Ax + (size_t)inst * P.nnzA;
   const double* l_in = p.l + (size_t)inst * m;
   const double* u_in = p.u + (size_t)inst * m;

@@ -62,7 +62,7 @@ using namespace mpcqp;
 
 extern "C" {
 
-int mpcqp_version(void) { return 100; }
+int mpcqp_version(void) { return 101; }
 const char* mpcqp_last_error(void) { return g_err.c_str(); }
 
 const char* mpcqp_status_string(int32_t st) {

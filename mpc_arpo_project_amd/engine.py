@@ -1,8 +1,9 @@
 """Batched torch front-end of the HIP engine.
 
-`BatchQP` owns one `mpcqp_handle`: B instances that share the sparsity of P and A (and the values
-of P and q) -- the shape of every MPC-QP the reference builds for one scenario family
-(reference src/trajectorySimulate.py:216-236).  All tensors are float64 / int32 on the GPU; the
+`BatchQP` owns one `mpcqp_handle`: B instances that share the sparsity of P and A -- the shape of
+every MPC-QP the reference builds for one scenario family (reference
+src/trajectorySimulate.py:216-236).  The values of P and q are shared by the batch too, unless they
+are given per instance ((B, nnzP) / (B, n): one cost-weight set per instance).  All tensors are float64 / int32 on the GPU; the
 engine never silently moves work to the CPU.
 """
 from __future__ import annotations
@@ -116,24 +117,50 @@ class BatchQP:
         self._inflight = tensors
 
     # ------------------------------------------------------------------------------------ API
+    def _cost(self, a, width, name):
+        """cost data shared by the batch, (width,), or per instance, (B, width) -> (tensor,
+        per instance?)"""
+        t = torch.as_tensor(a, dtype=torch.float64, device=self.device)
+        if tuple(t.shape) == (self.B, width):
+            return t.contiguous(), True
+        if t.dim() == 2 and t.numel() != width:
+            raise ValueError(f"{name} must have shape ({width},) or ({self.B}, {width})")
+        return self._t(t, (width,), name), False
+
     def set_data(self, Px=None, q=None, Ax=None, l=None, u=None):
-        Px = self._t(self.P.data if Px is None else Px, (self.nnzP,), "Px")
-        q = self._t(q, (self.n,), "q")
+        """Px (nnzP,) / q (n,) shared by the batch, or (B, nnzP) / (B, n): cost data per instance
+        (mpcqp_set_data_batched; a shared one beside a per-instance one is broadcast)."""
+        Px, bP = self._cost(self.P.data if Px is None else Px, self.nnzP, "Px")
+        q, bq = self._cost(q, self.n, "q")
         Ax = self._batch_vec(self.A.data if Ax is None else Ax, self.nnzA, "Ax")
         l = self._batch_vec(l, self.m, "l")
         u = self._batch_vec(u, self.m, "u")
         if bool((l > u).any()):
             raise ValueError("lower bound must be lower than or equal to upper bound")
-        check(_lib.lib().mpcqp_set_data(self._h, Px.data_ptr(), q.data_ptr(), Ax.data_ptr(),
-                                        l.data_ptr(), u.data_ptr()), "mpcqp_set_data")
+        if bP or bq:
+            Px = Px if bP else self._batch_vec(Px, self.nnzP, "Px")
+            q = q if bq else self._batch_vec(q, self.n, "q")
+            check(_lib.lib().mpcqp_set_data_batched(self._h, Px.data_ptr(), q.data_ptr(),
+                                                    Ax.data_ptr(), l.data_ptr(), u.data_ptr()),
+                  "mpcqp_set_data_batched")
+        else:
+            check(_lib.lib().mpcqp_set_data(self._h, Px.data_ptr(), q.data_ptr(), Ax.data_ptr(),
+                                            l.data_ptr(), u.data_ptr()), "mpcqp_set_data")
         self._keep(Px=Px, q=q, Ax=Ax, l=l, u=u)
         self._has_data = True
 
-    def update(self, q=None, l=None, u=None, Ax=None):
+    def update(self, q=None, l=None, u=None, Ax=None, Px=None):
+        """OSQP's update(), applied in its order: q, the bounds, then P, then A.  q (n,) or (B, n);
+        Px (nnzP,) or (B, nnzP), upper-triangular CSC order (osqp_update_P: mpcqp_update_P)."""
         keep = {}
         if q is not None:
-            q = self._t(q, (self.n,), "q")
-            check(_lib.lib().mpcqp_update_lin_cost(self._h, q.data_ptr()), "mpcqp_update_lin_cost")
+            q, bq = self._cost(q, self.n, "q")
+            if bq:
+                check(_lib.lib().mpcqp_update_lin_cost_batched(self._h, q.data_ptr()),
+                      "mpcqp_update_lin_cost_batched")
+            else:
+                check(_lib.lib().mpcqp_update_lin_cost(self._h, q.data_ptr()),
+                      "mpcqp_update_lin_cost")
             keep["q"] = q
         if l is not None or u is not None:
             if l is None or u is None:
@@ -145,6 +172,14 @@ class BatchQP:
             check(_lib.lib().mpcqp_update_bounds(self._h, l.data_ptr(), u.data_ptr()),
                   "mpcqp_update_bounds")
             keep.update(l=l, u=u)
+        if Px is not None:
+            Px, bP = self._cost(Px, self.nnzP, "Px")
+            if bP:
+                check(_lib.lib().mpcqp_update_P_batched(self._h, Px.data_ptr()),
+                      "mpcqp_update_P_batched")
+            else:
+                check(_lib.lib().mpcqp_update_P(self._h, Px.data_ptr()), "mpcqp_update_P")
+            keep["Px"] = Px
         if Ax is not None:
             Ax = self._batch_vec(Ax, self.nnzA, "Ax")
             check(_lib.lib().mpcqp_update_A(self._h, Ax.data_ptr()), "mpcqp_update_A")

@@ -8,6 +8,7 @@ src/trajectorySimulateC.py:269-272, :338, :399, :405), backed by the HIP engine 
     prob.setup(P, q, A, l, u, warm_start=True, verbose=False)
     res = prob.solve();  res.x, res.y, res.info.status ('solved', ...), res.info.iter
     prob.update(l=l, u=u);  prob.update(Ax=A.data, l=l, u=u)
+    prob.update(Px=triu(P).data)  /  prob.update(Px=values, Px_idx=positions)
 
 Argument meaning and error behaviour follow osqp: dimension mismatches and l > u raise
 ValueError; infeasibility / non-convergence are reported through `res.info.status`, never raised.
@@ -48,6 +49,7 @@ class OSQP:
             raise ValueError("lower bound must be lower than or equal to upper bound")
         self.n, self.m = n, m
         self._A = A
+        self._Px = np.array(P.data, dtype=float)  # upper-triangular CSC values (update(Px=...))
         self._l, self._u = l.copy(), u.copy()
         self._qp = BatchQP(P, A, batch=1, device=self._device, **settings)
         self._qp.set_data(Px=P.data, q=q, Ax=A.data, l=l, u=u)
@@ -56,8 +58,17 @@ class OSQP:
                Ax_idx=np.array([])):
         if self._qp is None:
             raise ValueError("setup must be called first")
-        if Px is not None:
-            raise NotImplementedError("P values are shared by the batch; the reference never updates P")
+        if Px is not None:  # validated here, sent after the bounds (osqp's order: q, l / u, P, A)
+            Px = np.asarray(Px, dtype=float).reshape(-1)
+            Px_idx = np.asarray(Px_idx)
+            if len(Px_idx):
+                if len(Px_idx) != len(Px):
+                    raise ValueError("Px and Px_idx must have the same lengths")
+                full = self._Px.copy()
+                full[Px_idx] = Px
+                Px = full
+            if Px.shape != self._Px.shape:
+                raise ValueError("Px must have nnz(triu(P)) entries")
         if q is not None:
             q = np.asarray(q, dtype=float).reshape(-1)
             if q.shape != (self.n,):
@@ -78,6 +89,9 @@ class OSQP:
                 raise ValueError("lower bound must be lower than or equal to upper bound")
             self._l, self._u = nl.copy(), nu.copy()
             self._qp.update(l=nl, u=nu)
+        if Px is not None:
+            self._Px[:] = Px
+            self._qp.update(Px=Px)
         if Ax is not None:
             Ax = np.asarray(Ax, dtype=float).reshape(-1)
             Ax_idx = np.asarray(Ax_idx)

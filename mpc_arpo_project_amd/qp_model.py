@@ -502,3 +502,58 @@ def configure_batch(prob: MPCProblem, xest_batch):
     l[:, r3:r3 + prob.ndi] = d
     u[:, r3:r3 + prob.ndi] = d
     return Ax, l, u
+
+
+# ------------------------------------------------------------------------------------------------
+# cost-weight variants of one scenario family (one batch, one weight set per instance)
+# ------------------------------------------------------------------------------------------------
+
+# everything the closed-loop kernels' scenario description reads (closed_loop.scenario_struct) and
+# the per-step reconfiguration above uses, in the order it is compared
+_VARIANT_FIELDS = ("nx", "nu", "ny", "ndi", "Nx", "Nc", "Nb", "has_debris", "inTrack", "isReject",
+                   "T", "Ad", "Bd", "rp", "rtol", "xr", "umin", "umax", "center", "side", "detect",
+                   "verts", "Kpf", "Kif", "K_total", "K_i", "Crefx", "Crefy")
+
+
+def _same(a, b):
+    if a is None or b is None:
+        return a is None and b is None
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and bool(np.array_equal(a, b))
+
+
+def cost_variants(probs):
+    """Stack the cost data of problems that differ only in their weights (Q_state, R_input, R_slack
+    of MPCParams), so that one batch -- one BatchQP, one closed-loop handle -- can hold a mix of
+    them: returns Px [V, nnzP] (upper triangle, sorted CSC, as engine.triu_csc orders it), q [V, n]
+    and the constant A values [V, nnzA] (the terminal LQR gain K of construct_aeq follows the
+    weights, so A's constant values do; the per-step varying positions hold placeholders).
+
+    Raises ValueError naming the first field in which a problem differs from probs[0]: the
+    dimensions, every scenario constant the closed-loop kernels and configure_batch read, the
+    patterns of P and A, the positions of the varying A values and the set-up bounds."""
+    from .engine import triu_csc
+
+    probs = list(probs)
+    if not probs:
+        raise ValueError("cost_variants needs at least one problem")
+    p0 = probs[0]
+    P0 = triu_csc(p0.P)
+    Px, q, Ax = [], [], []
+    for v, p in enumerate(probs):
+        for f in _VARIANT_FIELDS:
+            if not _same(getattr(p, f), getattr(p0, f)):
+                raise ValueError(f"problem {v} is not batch-compatible with problem 0: {f} differs")
+        Pv = triu_csc(p.P)
+        for name, a, b in (("P", Pv, P0), ("A", p.A, p0.A)):
+            if a.shape != b.shape or not (np.array_equal(a.indptr, b.indptr) and
+                                          np.array_equal(a.indices, b.indices)):
+                raise ValueError(f"problem {v} is not batch-compatible with problem 0: "
+                                 f"the sparsity pattern of {name} differs")
+        for f in ("pos_c1", "pos_c2", "pos_slope", "l", "u"):
+            if not _same(getattr(p, f), getattr(p0, f)):
+                raise ValueError(f"problem {v} is not batch-compatible with problem 0: {f} differs")
+        Px.append(np.asarray(Pv.data, dtype=float))
+        q.append(np.asarray(p.q, dtype=float))
+        Ax.append(np.asarray(p._base_data, dtype=float))
+    return np.stack(Px), np.stack(q), np.stack(Ax)

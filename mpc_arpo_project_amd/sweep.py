@@ -37,6 +37,16 @@ x0 = (100, 10, 0, 0)):
         test/saved_runs/success_rates_test.py:46-75: Nx = 40, T_final = 300, noise sigma 0.3
         held 50 samples, isReject = True; the count of isSuccess runs
 
+Cost-weight variants (no reference counterpart: its weights were tuned by re-running the scripts
+by hand): `--q-scale 0.25,1,4 --r-scale 1,4 --rs-scale 1` runs every (seed, initial condition)
+scenario once per weight set, the product of the lists, each a triple of multipliers of the
+scenario's Q_state, R_input, R_slack.  With V weight sets the sweep has G = V * G0 chasers, G0 =
+n_seeds * n_ics; global id g = v * G0 + g0 runs weight set v on initial condition g0 % n_ics under
+noise stream g0 (mpcqp_cl_set_id_period(G0)), so every weight set sees the same initial conditions
+and noise realisations (common random numbers).  Ranks and shards stay contiguous in g -- one may
+hold several weight sets, in one batch (per-instance P and q, mpcqp_set_data_batched).  The summary
+keeps its [G, 9] layout; the JSON line gains "variants": the headline statistics per weight set.
+
   --noise-stream reference (default): the reference's own noise.  trajectorySimulate re-seeds
         numpy's global generator with 123 at every call (src/trajectorySimulate.py:28) and draws
         noiseVec = sigMat @ normal(0, 1, 4) from it (:268, :352-356), so every Monte-Carlo run of
@@ -103,7 +113,9 @@ def scenario_states(scenario: str, n_seeds: int, n_ics: int, lo: int, hi: int, i
     return ics[g % n_ics]
 
 
-def build(scenario: str, Nx: int, noise, isReject: bool, T_final: float):
+def build(scenario: str, Nx: int, noise, isReject: bool, T_final: float, weights=None):
+    """(sim, problem) of the approach; weights: (q_scale, r_scale, rs_scale) multipliers of the
+    scenario's Q_state, R_input, R_slack (None: the scenario's own)"""
     from . import qp_model
     from .mpcsim import Noise
 
@@ -114,7 +126,20 @@ def build(scenario: str, Nx: int, noise, isReject: bool, T_final: float):
     else:
         sim, mpc, fail, deb = scenarios.in_track_scenario(Nx=Nx, isReject=isReject, noise=nz,
                                                           T_final=T_final)
+    if weights is not None:
+        qs, rs, ss = (float(w) for w in weights)
+        if min(qs, rs, ss) <= 0:
+            raise ValueError("weight multipliers must be positive")
+        mpc.Q_state, mpc.R_input, mpc.R_slack = mpc.Q_state * qs, mpc.R_input * rs, mpc.R_slack * ss
     return sim, qp_model.build_problem(sim, mpc, fail, deb)
+
+
+def variant_index(lo: int, hi: int, G0: int, n_ics: int):
+    """global ids [lo, hi) of a sweep with weight sets -> (v, g0, ic, key) arrays: g = v * G0 + g0
+    runs weight set v on initial condition ic = g0 % n_ics under noise stream key = g0"""
+    g = np.arange(lo, hi)
+    g0 = g % G0
+    return g // G0, g0, g0 % n_ics, g0
 
 
 class Sweep:
@@ -123,20 +148,38 @@ class Sweep:
     def __init__(self, scenario="radial", n_seeds=1, n_ics=1024, Nx=40, noise=(0.75, 0.75, 50),
                  isReject=True, T_final=150.0, rank=0, world=1, device="cuda", shards=2,
                  ic_seed=20250328, noise_seed=123, eps=1e-3, keep_traj=False, x0=None,
-                 noise_source=None):
+                 noise_source=None, variants=None, weights=None):
+        """variants: a list of (q_scale, r_scale, rs_scale) weight sets, every scenario once per
+        set (module docstring); weights: one such triple for a plain sweep (shared cost data)"""
         import torch
 
         from .closed_loop import ShardedClosedLoop
 
-        self.G = n_seeds * n_ics
+        self.G0 = n_seeds * n_ics
+        self.V = 1 if variants is None else len(variants)
+        if self.V < 1:
+            raise ValueError("variants must name at least one weight set")
+        self.G = self.V * self.G0
         self.lo, self.hi = launch.shard_range(self.G, rank, world)
-        self.sim, self.prob = build(scenario, Nx, noise, isReject, T_final)
+        kw = {}
+        if variants is not None and weights is not None:
+            raise ValueError("give the weight sets either as variants or as one weights triple")
+        if variants is None:
+            self.sim, self.prob = build(scenario, Nx, noise, isReject, T_final, weights)
+            X = scenario_states(scenario, n_seeds, n_ics, self.lo, self.hi, ic_seed, x0)
+        else:
+            if noise_source is not None:
+                raise ValueError("a host noise source draws per batch row: not with variants")
+            built = [build(scenario, Nx, noise, isReject, T_final, w) for w in variants]
+            self.sim, self.prob = built[0][0], [b[1] for b in built]
+            v, g0, _, _ = variant_index(self.lo, self.hi, self.G0, n_ics)
+            X = scenario_states(scenario, n_seeds, n_ics, 0, self.G0, ic_seed, x0)[g0]
+            kw = dict(variant=v, id_period=self.G0)
         self.nsim = int(self.sim.T_final / self.sim.time_stp)
-        X = scenario_states(scenario, n_seeds, n_ics, self.lo, self.hi, ic_seed, x0)
         # the reference's default OSQP tolerances (eps_abs = eps_rel = 1e-3) unless asked otherwise
         self.loop = ShardedClosedLoop(self.prob, X, shards=shards, device=device, id_offset=self.lo,
                                       noise=noise, noise_seed=noise_seed, eps_abs=eps, eps_rel=eps,
-                                      noise_source=noise_source)
+                                      noise_source=noise_source, **kw)
         self.loop.enable_tracking(self.nsim, *self.sim.suc_cond)
         self.traj = None
         if keep_traj:
@@ -202,6 +245,14 @@ def reduce(S: np.ndarray):
                 fallback_step_frac=float(f["n_fallback"].sum() / max(1, it.sum())),
                 admm_iters_total=float(f["admm_iters"].sum()),
                 last_status={int(a): int(b) for a, b in zip(st, cnt)})
+
+
+def reduce_variants(S: np.ndarray, V: int):
+    """reduce() of each weight set's block of a gathered [V * G0, 9] summary (g = v * G0 + g0)"""
+    if V < 1 or S.shape[0] % V:
+        raise ValueError(f"{S.shape[0]} summary rows do not split into {V} weight sets")
+    G0 = S.shape[0] // V
+    return [reduce(S[v * G0:(v + 1) * G0]) for v in range(V)]
 
 
 X0_REF = (100., 10., 0., 0.)  # x0 of test/disturbRejComp.py:37 and success_rates_test.py:37
@@ -308,7 +359,17 @@ def main(argv=None):
     ap.add_argument("--noise-stream", choices=("reference", "independent"), default="reference",
                     help="experiments: the reference's seed-123 stream for every run, or a "
                          "stream per run (module docstring)")
+    for flag, what in (("--q-scale", "Q_state"), ("--r-scale", "R_input"), ("--rs-scale", "R_slack")):
+        ap.add_argument(flag, default=None,
+                        help=f"comma list of multipliers of the scenario's {what}; the weight sets "
+                             "of the sweep are the product of the three lists (module docstring)")
     a = ap.parse_args(argv[1:])
+    variants = None
+    if a.q_scale or a.r_scale or a.rs_scale:
+        if a.experiment:
+            ap.error("--q-scale / --r-scale / --rs-scale do not combine with --experiment")
+        lists = [[float(x) for x in (v or "1").split(",")] for v in (a.q_scale, a.r_scale, a.rs_scale)]
+        variants = [(qs, rs, ss) for qs in lists[0] for rs in lists[1] for ss in lists[2]]
     dflt = SCENARIO_DEFAULTS[a.scenario]
     a.nx = dflt["nx"] if a.nx is None else a.nx
     a.noise = dflt["noise"] if a.noise is None else a.noise
@@ -335,7 +396,7 @@ def main(argv=None):
         noise = (noise[0], noise[1], int(noise[2]))
     sw = Sweep(a.scenario, a.seeds, a.ics, Nx=a.nx, noise=noise, isReject=not a.no_reject,
                T_final=a.tfinal, rank=rank, world=world, device=device, shards=a.shards,
-               eps=a.eps, keep_traj=a.traj)
+               eps=a.eps, keep_traj=a.traj, variants=variants)
     el = _timed_run(sw, dist, device)
     local_sum = sw.summary()
     S = launch.gather_rows(local_sum, sw.G, rank, world, dist)
@@ -351,6 +412,9 @@ def main(argv=None):
         out.update(scenario=a.scenario, n_gpus=world, seeds=a.seeds, ics=a.ics, nx=a.nx,
                    noise=a.noise, reject=not a.no_reject, steps=sw.steps, seconds=el,
                    scenarios_per_s=sw.G / el, solves_per_s=solved_steps / el)
+        if variants is not None:
+            out["variants"] = [dict(q_scale=w[0], r_scale=w[1], rs_scale=w[2], **r)
+                               for w, r in zip(variants, reduce_variants(Sn, len(variants)))]
         if a.out:
             np.save(a.out, Sn)
             if traj is not None:
