@@ -13,6 +13,7 @@
 
 #include "../../include/mpcqp_closed_loop.h"
 #include "../../include/mpcqp_estimation.h"
+#include "host_abi.hpp"
 #include "plant_dev.hpp"
 
 namespace {
@@ -359,7 +360,11 @@ __global__ void __launch_bounds__(64) clc_period_kernel(
   up[1] = c1;
 }
 
-thread_local std::string g_cl_err;
+using mpcqp::set_error;
+int launched(const char* entry) {  // the return code of an entry point that has launched its kernel
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : set_error(MPCQP_E_HIP, std::string(entry) + ": " + hipGetErrorString(e));
+}
 
 }  // namespace
 
@@ -378,26 +383,23 @@ struct mpcqp_cl {
 extern "C" {
 
 int mpcqp_cl_create(const mpcqp_cl_scenario* sc, int32_t batch, void* stream, mpcqp_cl** out) {
-  if (!sc || !out || batch <= 0 || sc->Nx < sc->Nc || sc->Nx < sc->Nb) return -1;
+  if (!sc || !out || batch <= 0 || sc->Nx < sc->Nc || sc->Nx < sc->Nb)
+    return set_error(MPCQP_E_INVALID, "mpcqp_cl_create: invalid argument");
   *out = nullptr;
   mpcqp_cl* cl = new mpcqp_cl();
   cl->d.sc = *sc;
   cl->d.B = batch;
   cl->stream = (hipStream_t)stream;
   const int np = sc->Nx + 1;
-  if (hipMalloc(&cl->dpos, sizeof(int32_t) * 3 * np) != hipSuccess) {
-    delete cl;
-    return -2;
-  }
+  auto fail = [cl](const char* msg) { return mpcqp_cl_destroy(cl), set_error(MPCQP_E_HIP, msg); };
+  if (hipMalloc(&cl->dpos, sizeof(int32_t) * 3 * np) != hipSuccess)
+    return fail("mpcqp_cl_create: hipMalloc(positions)");
   if (hipMemcpy(cl->dpos, sc->pos_c1, sizeof(int32_t) * np, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(cl->dpos + np, sc->pos_c2, sizeof(int32_t) * np, hipMemcpyHostToDevice) !=
           hipSuccess ||
       (sc->pos_slope && hipMemcpy(cl->dpos + 2 * np, sc->pos_slope, sizeof(int32_t) * np,
-                                  hipMemcpyHostToDevice) != hipSuccess)) {
-    (void)hipFree(cl->dpos);
-    delete cl;
-    return -2;
-  }
+                                  hipMemcpyHostToDevice) != hipSuccess))
+    return fail("mpcqp_cl_create: hipMemcpy(positions)");
   cl->d.pos_c1 = cl->dpos;
   cl->d.pos_c2 = cl->dpos + np;
   cl->d.pos_slope = sc->pos_slope ? cl->dpos + 2 * np : nullptr;
@@ -414,11 +416,11 @@ int mpcqp_cl_destroy(mpcqp_cl* cl) {
 }
 
 int mpcqp_cl_configure(mpcqp_cl* cl, double* xest, double* Ax, double* l, double* u) {
-  if (!cl || !xest || !Ax || !l || !u) return -1;
+  if (!cl || !xest || !Ax || !l || !u) return set_error(MPCQP_E_INVALID, "mpcqp_cl_configure: null argument");
   const int B = cl->d.B;
   hipLaunchKernelGGL(cl_configure_kernel, dim3((B + 255) / 256), dim3(256), 0, cl->stream, cl->d,
                      xest, Ax, l, u);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
+  return launched("mpcqp_cl_configure");
 }
 
 int mpcqp_cl_step(mpcqp_cl* cl, const int32_t* status, const double* x_sol, int32_t n,
@@ -427,20 +429,21 @@ int mpcqp_cl_step(mpcqp_cl* cl, const int32_t* status, const double* x_sol, int3
                   const double* noise, double* z, double* u_applied) {
   if (!cl || !status || !x_sol || !x_true || !ctrl_prev || !xintf || !xest || !done ||
       !ctrl_seq || !ctrl_out)
-    return -1;
+    return set_error(MPCQP_E_INVALID, "mpcqp_cl_step: null argument");
   const int B = cl->d.B;
   cl->d.tr.step = cl->steps++;
   hipLaunchKernelGGL(cl_step_kernel, dim3((B + 255) / 256), dim3(256), 0, cl->stream, cl->d,
                      status, x_sol, n, u0_offset, x_true, ctrl_prev, xintf, xest, done, ctrl_seq,
                      ctrl_out, noise, z, u_applied);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
+  return launched("mpcqp_cl_step");
 }
 
 int mpcqp_cl_set_tracking(mpcqp_cl* cl, int32_t* iterm, int32_t* success, double* final_err,
                           int32_t* n_fallback, double dist_tol, double ang_tol) {
-  if (!cl) return -1;
+  if (!cl) return set_error(MPCQP_E_INVALID, "mpcqp_cl_set_tracking: null handle");
   const bool any = iterm || success || final_err || n_fallback;
-  if (any && !(iterm && success && final_err && n_fallback)) return -1;
+  if (any && !(iterm && success && final_err && n_fallback))
+    return set_error(MPCQP_E_INVALID, "mpcqp_cl_set_tracking: all four buffers or none");
   Track& t = cl->d.tr;
   t.iterm = iterm, t.success = success, t.final_err = final_err, t.n_fallback = n_fallback;
   t.dist_tol = dist_tol, t.ang_tol = ang_tol;
@@ -449,28 +452,28 @@ int mpcqp_cl_set_tracking(mpcqp_cl* cl, int32_t* iterm, int32_t* success, double
 }
 
 int mpcqp_cl_set_ids(mpcqp_cl* cl, int64_t id0) {
-  if (!cl || id0 < 0) return -1;
+  if (!cl || id0 < 0) return set_error(MPCQP_E_INVALID, "mpcqp_cl_set_ids: invalid argument");
   cl->id0 = id0;
   return 0;
 }
 
 int mpcqp_cl_set_id_period(mpcqp_cl* cl, int64_t period) {
-  if (!cl || period < 0) return -1;
+  if (!cl || period < 0) return set_error(MPCQP_E_INVALID, "mpcqp_cl_set_id_period: invalid argument");
   cl->id_period = period;
   return 0;
 }
 
 int mpcqp_cl_noise(mpcqp_cl* cl, uint64_t seed, uint64_t draw, double sig_x, double sig_y,
                    double* noise) {
-  if (!cl || !noise) return -1;
+  if (!cl || !noise) return set_error(MPCQP_E_INVALID, "mpcqp_cl_noise: null argument");
   const int B = cl->d.B;
   hipLaunchKernelGGL(cl_noise_kernel, dim3((B + 255) / 256), dim3(256), 0, cl->stream, B, seed,
                      cl->id0, cl->id_period, draw, sig_x, sig_y, noise);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
+  return launched("mpcqp_cl_noise");
 }
 
 int mpcqp_cl_set_plant(mpcqp_cl* cl, const mpcqp_plant_model* m, int32_t isDeltaV) {
-  if (!cl || !m) return -1;
+  if (!cl || !m) return set_error(MPCQP_E_INVALID, "mpcqp_cl_set_plant: null argument");
   cl->pc = PlantConsts{m->two_n, m->m_two_n, m->n2, m->R_T, m->mu, m->g0, m->rtol, m->atol};
   cl->isDeltaV = isDeltaV ? 1 : 0;
   cl->has_plant = true;
@@ -484,13 +487,13 @@ int mpcqp_clc_period(mpcqp_cl* cl, const int32_t* status, const double* x_sol, i
                      double t_start, double dt, int32_t i_start, int32_t nsub, double* traj) {
   if (!cl || !cl->has_plant || !status || !x_sol || !x_true || !ctrl_prev || !xintf || !xest ||
       !done || !iterm || !ctrl_seq || !ctrl_out || nsub < 1 || !(dt > 0.0))
-    return -1;
+    return set_error(MPCQP_E_INVALID, "mpcqp_clc_period: invalid argument or no plant set");
   const int B = cl->d.B;
   hipLaunchKernelGGL(clc_period_kernel, dim3((B + 63) / 64), dim3(64), 0, cl->stream, cl->d,
                      cl->pc, cl->isDeltaV, status, x_sol, n, u0_offset, x_true, ctrl_prev, xintf,
                      xest, done, iterm, ctrl_seq, ctrl_out, noise, z, u_applied, t_start, dt,
                      i_start, nsub, traj);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
+  return launched("mpcqp_clc_period");
 }
 
 }  // extern "C"

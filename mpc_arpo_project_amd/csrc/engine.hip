@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/mpcqp.h"
+#include "dev_plan.hpp"
 #include "host_abi.hpp"
 #include "symbolic.hpp"
 
@@ -54,37 +55,6 @@ using namespace mpcqp;
 namespace {
 
 // ------------------------------------------------------------------------------------- device
-struct EllDev {
-  const uint16_t *src, *in, *vpos, *sk;
-  const uint32_t* pk;  // lane-major packed (vpos, in) terms of the used slots (symbolic.hpp Ell::pk)
-  int K[ELL_MAXR], off[ELL_MAXR];
-  int total, nlong;
-  int long_out[ELL_MAXLONG], long_off[ELL_MAXLONG], long_cnt[ELL_MAXLONG];
-};
-struct DevPlan {
-  EllDev eA, eAt, eP;  // residual mat-vecs (symbolic.hpp Ell)
-  const uint32_t *fac, *tail, *fwd, *bwd;  // fixed-stride step records (symbolic.hpp)
-  // KM_MREG kernels: the solve records split into vector-operand + target records (fwdc, bwdc) and
-  // the matrix operands' LDS addresses (fwdm, bwdm), built on the host (mpcqp_create)
-  const uint32_t *fwdc, *bwdc, *fwdm, *bwdm;
-  int nfac, ntail, nfwd, nbwd;
-  const uint16_t* Lcol;    // DINV slot of each L entry's column
-  int inst_doubles;        // LDS doubles of the instance image (16-byte aligned)
-  const uint16_t *slotP, *slotA, *slotRho, *slotSig, *wsx, *wsz;
-  const uint16_t *Ap, *Ai, *Acol, *Arp, *Ark, *Arj, *Pi, *Pcol, *Psp, *Psk, *Pso;
-  int n, m, nk, nnzP, nnzA, nnzL;
-  int LX, DINV, W, CACC, ZERO, ONE, MONE, LDS_N, S_P, S_A, S_DT, S_ET;
-  int NKS;  // 64-lane slots of the padded 1/D, W and C regions (symbolic.hpp NKP / 64 = RN + RM)
-  const uint32_t* wcopy;  // per lane: register slots whose W starts at the rhs (symbolic.hpp Plan::wcopy)
-  const uint32_t* bcopy;  // per lane: diagonal-pass slots whose W starts at (1/D) W (Plan::bcopy)
-  int S_ZERO;
-  int MV, MVZ;  // resident scaled values [P | A] (CSC orders) and their zero slot
-  int mv_slab;  // doubles of the per-wave slab holding them instead (Plan::mv_global), else 0
-  const uint16_t *sra, *sca;  // lane-major row / column scaling slots (symbolic.hpp Plan::sra)
-  int SJ;
-  int XCH, XID;  // two-wave kernel: exchange slots and the handed-over instance id (Plan::XCH)
-};
-
 struct KParams {
   DevPlan pl;
   mpcqp_settings s;
@@ -358,10 +328,10 @@ __device__ __forceinline__ double group_sum(double acc, uint32_t glog, uint32_t 
 
 // Schedule records are read through buffer descriptors: table base and size in SGPRs, the step
 // offset in an SGPR (soffset), the lane's offset a constant VGPR, so no record address is computed
-// per step.  Every table is followed by TABLE_PAD_STEPS zero steps in device memory (push_table), so
+// per step.  Every table is followed by TABLE_PAD_STEPS zero steps in device memory (build_dev_image), so
 // the record pipelines load steps up to n + 2 unclamped and in range (round 5: the clamp's n - 1
 // was an SGPR the two-wave kernel spilled, one v_readlane per solve step, +21 % forward-solve time).
-constexpr int TABLE_PAD_STEPS = 3;
+// TABLE_PAD_STEPS: dev_plan.hpp.
 typedef __amdgpu_buffer_rsrc_t Rsrc;
 __device__ __forceinline__ Rsrc table_rsrc(const uint32_t* tbl, int nsteps, int stride_words) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(tbl), (short)0,
@@ -599,14 +569,11 @@ __device__ __forceinline__ void run_body_pf(Rsrc rs, int n, uint32_t lane, doubl
 // waves per CU: 342 -> 258 cycles per wave-step).  The host splits each term into its vector
 // address (in W or C) and its matrix address (anything else) -- the product is commutative and
 // fma(-x1, y1, -(x0 y0)) does not depend on the operands' order, so the results are bit-identical
-// to the LDS-operand kernel on the same plan.
-constexpr int MREG_STEPS = 6;
+// to the LDS-operand kernel on the same plan.  (MREG_STEPS and the record strides: dev_plan.hpp.)
 struct MatRegs {
   double m[2][MREG_STEPS][SOLVE_MAXC];  // [forward / backward][step][term]
 };
-// compact step record: vector addresses of the 8 terms, then the 4 targets (3 rows of 64 lane quads)
-constexpr int SOLVEC_STEP_WORDS = 3 * 64 * 4;
-constexpr int SOLVEM_STEP_WORDS = 2 * 64 * 4;  // matrix addresses of the 8 terms (2 rows)
+// compact step record (SOLVEC_STEP_WORDS): vector addresses of the 8 terms, then the 4 targets
 struct SolveRecC {
   uint32_t b[SOLVE_MAXC];
   uint32_t t0, t1, t2, t3;
@@ -2071,25 +2038,21 @@ __global__ void update_P_kernel(double* setup, int setup_stride, double* W, cons
 }
 
 // ---------------------------------------------------------------------------------------- host
-int fail(int code, const std::string& msg) { return set_error(code, msg); }
 #define HIPCHK(x)                                                                   \
   do {                                                                              \
     hipError_t e_ = (x);                                                            \
-    if (e_ != hipSuccess) return fail(MPCQP_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
+    if (e_ != hipSuccess) return set_error(MPCQP_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
   } while (0)
 
 typedef void (*kernel_fn)(KParams);
 
-// block caps of the blocked substitution (symbolic.hpp); MPCQP_CAPM / MPCQP_CAPW override them.
 // Every MPCQP_* override below is a diagnostic: honoured only with MPCQP_DIAGNOSTICS=1 (diag_env)
-int env_int(const char* name, int dflt) { return diag_env_int(name, dflt); }
-
 template <int RN, int RM>
 kernel_fn pick(bool paired, int waves, bool matpf, bool mvg, bool mreg) {
   // two waves, the solve steps on the first; MPCQP_W0DIAG=1: the diagonal pass too (mode 3,
   // measured equal to mode 2 at N = 40)
   if (waves == 3)
-    return env_int("MPCQP_W0DIAG", 0)
+    return diag_env_int("MPCQP_W0DIAG", 0)
                ? (paired ? qp_pair_kernel<RN / 2, RM / 2, true, 3> : qp_pair_kernel<RN / 2, RM / 2, false, 3>)
                : (paired ? qp_pair_kernel<RN / 2, RM / 2, true, 2> : qp_pair_kernel<RN / 2, RM / 2, false, 2>);
   if (waves == 2) {
@@ -2142,65 +2105,7 @@ bool use_mreg(const Plan& pl) {
   int rn = 0, rm = 0;
   const bool fits = pl.waves == 1 && !pl.mat_first && !pl.mv_global && pl.nfwd <= MREG_STEPS &&
                     pl.nbwd <= MREG_STEPS && kernel_bucket(pl.n, pl.m, rn, rm) && rn == 2;
-  return fits && env_int("MPCQP_MREG", MREG_DEFAULT) != 0;
-}
-// the KM_MREG record tables from the plan's solve records: per step, the terms' vector addresses
-// (the operand in the W or C region) + the targets (SolveRecC), and the terms' matrix addresses
-// (every other operand: L, N | G | G', ZERO / ONE / MONE); a padding term (both operands zero
-// slots) reads its matrix zero from the first and its vector zero from the second
-void split_records(const Plan& pl, const std::vector<uint32_t>& rec, int nsteps,
-                   std::vector<uint32_t>& vec, std::vector<uint32_t>& mat) {
-  auto is_vec = [&](uint32_t byte) {
-    const int d = (int)(byte / 8u);
-    return (d >= pl.W && d < pl.W + pl.NKP) || (d >= pl.CACC && d < pl.CACC + pl.NKP);
-  };
-  vec.assign((size_t)nsteps * SOLVEC_STEP_WORDS, 0u);
-  mat.assign((size_t)nsteps * SOLVEM_STEP_WORDS, 0u);
-  for (int st = 0; st < nsteps; ++st) {
-    const uint32_t* r = rec.data() + (size_t)st * SOLVE_STEP_WORDS;
-    uint32_t* cv = vec.data() + (size_t)st * SOLVEC_STEP_WORDS;
-    uint32_t* cm = mat.data() + (size_t)st * SOLVEM_STEP_WORDS;
-    for (int l = 0; l < 64; ++l) {
-      for (int c = 0; c < SOLVE_MAXC; ++c) {
-        // full record: row q = c / 2 holds lane quads (a_2q, b_2q, a_2q+1, b_2q+1)
-        const uint32_t a = r[(c / 2) * 256 + l * 4 + (c % 2) * 2];
-        const uint32_t b = r[(c / 2) * 256 + l * 4 + (c % 2) * 2 + 1];
-        const bool av = is_vec(a);
-        // compact rows: q = c / 4 holds lane quads of terms 4q..4q+3
-        cv[(c / 4) * 256 + l * 4 + (c % 4)] = av ? a : b;
-        cm[(c / 4) * 256 + l * 4 + (c % 4)] = av ? b : a;
-      }
-      for (int k = 0; k < 4; ++k) cv[2 * 256 + l * 4 + k] = r[SOLVE_TERM_WORDS + l * 4 + k];
-    }
-  }
-}
-
-template <typename T>
-size_t push_blob(std::vector<char>& blob, const std::vector<T>& v, size_t zero_tail = 0) {
-  size_t off = (blob.size() + 15) & ~size_t(15);
-  blob.resize(off + (v.size() + zero_tail) * sizeof(T) + 16);  // resize zero-fills the tail
-  if (!v.empty()) memcpy(blob.data() + off, v.data(), v.size() * sizeof(T));
-  return off;
-}
-// a schedule table and the TABLE_PAD_STEPS zero steps behind it (table_rsrc)
-size_t push_table(std::vector<char>& blob, const std::vector<uint32_t>& v, int stride_words) {
-  return push_blob(blob, v, (size_t)TABLE_PAD_STEPS * stride_words);
-}
-// Two tables that run one after the other (forward then backward solve; factorization then its
-// block-inverse tail), laid out as [A][B][the first TABLE_PAD_STEPS steps of A]: the record
-// pipelines' look-ahead loads past the end of A read B's first steps -- the very lines B's own
-// prefetch loads next, then L1 hits -- and B's read A's, which the next iteration loads (the
-// look-ahead loads are never executed, so their content does not matter).  Measured neutral on the
-// N = 20 bench (945k vs 944k solves/s: the shared zero pads were already L1-resident; DESIGN.md,
-// Record traffic), kept because it takes the pads' lines out of the L1 working set.
-void push_chain(std::vector<char>& blob, const std::vector<uint32_t>& A, const std::vector<uint32_t>& B,
-                int stride_words, size_t& oA, size_t& oB) {
-  const size_t pad = (size_t)TABLE_PAD_STEPS * stride_words;
-  std::vector<uint32_t> all(A);
-  all.insert(all.end(), B.begin(), B.end());
-  for (size_t k = 0; k < pad; ++k) all.push_back(k < A.size() ? A[k] : 0u);
-  oA = push_blob(blob, all, pad);
-  oB = oA + A.size() * sizeof(uint32_t);
+  return fits && diag_env_int("MPCQP_MREG", MREG_DEFAULT) != 0;
 }
 
 }  // namespace
@@ -2210,7 +2115,8 @@ struct mpcqp_handle {
   mpcqp_settings set;
   int B = 0;
   hipStream_t stream = nullptr;
-  char* d_blob = nullptr;
+  std::vector<void*> owned;  // every device allocation of the handle (dev_alloc; mpcqp_destroy)
+  char* d_blob = nullptr;    // the plan's device image (dev_plan.hpp), dp pointing into it
   DevPlan dp{};
   double *Px = nullptr, *q = nullptr, *Ax = nullptr, *l = nullptr, *u = nullptr;
   // per-instance set-up data [B][nnzP], [B][n]: allocated by the first batched call (batched_rows),
@@ -2235,250 +2141,152 @@ struct mpcqp_handle {
   kernel_fn kern = nullptr;
 };
 
+// device memory owned by the handle: recorded, and freed by mpcqp_destroy
+template <typename T>
+static bool dev_alloc(mpcqp_handle* h, T*& ptr, size_t bytes) {
+  void* p = nullptr;
+  if (hipMalloc(&p, bytes) != hipSuccess) return false;
+  h->owned.push_back(ptr = (T*)p);
+  return true;
+}
+// count elements, device to device, on the handle's stream
+template <typename T>
+static hipError_t copy_rows(const mpcqp_handle* h, T* dst, const T* src, size_t count) {
+  return hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyDeviceToDevice, h->stream);
+}
+// a helper kernel with a thread per element in blocks of 256, on the handle's stream
+template <typename... P, typename... A>
+static hipError_t launch_1d(const mpcqp_handle* h, void (*kern)(P...), size_t elements, A... args) {
+  if (elements == 0) return hipSuccess;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((elements + 255) / 256)), dim3(256), 0, h->stream, args...);
+  return hipGetLastError();
+}
+// the entry points' preamble: 0, or the error of a null handle / argument (args: the data pointers
+// are all there) or of a call that needs set_data first (the message: `what` before set_data)
+static int guard(const mpcqp_handle* h, bool args = true, const char* what = nullptr) {
+  if (!h || !args) return set_error(MPCQP_E_INVALID, h ? "null argument" : "null handle");
+  if (what && !h->has_data) return set_error(MPCQP_E_NODATA, std::string(what) + " before set_data");
+  return 0;
+}
+// the set-up P values and q with their strides (KParams::Px): one shared row, or a row per instance
+struct SetupRows {
+  double *Px, *q;
+  int Px_stride, q_stride;
+};
+static SetupRows setup_rows(const mpcqp_handle* h, bool batched) {
+  return batched ? SetupRows{h->PxB, h->qB, h->plan.nnzP, h->plan.n} : SetupRows{h->Px, h->q, 0, 0};
+}
+
 extern "C" {
 
 int mpcqp_create(const mpcqp_structure* st, const mpcqp_settings* s, int32_t batch, void* stream,
                  mpcqp_handle** out) {
-  if (!st || !s || !out || batch <= 0) return fail(MPCQP_E_INVALID, "invalid argument");
+  if (!st || !s || !out || batch <= 0) return set_error(MPCQP_E_INVALID, "invalid argument");
   *out = nullptr;
-  if (st->m <= 0) return fail(MPCQP_E_UNSUPPORTED, "problems without constraints (m == 0)");
-  if (s->polish) return fail(MPCQP_E_UNSUPPORTED, "polish is not implemented in this build");
+  if (st->m <= 0) return set_error(MPCQP_E_UNSUPPORTED, "problems without constraints (m == 0)");
+  if (s->polish) return set_error(MPCQP_E_UNSUPPORTED, "polish is not implemented in this build");
   if (s->scaled_termination)
-    return fail(MPCQP_E_UNSUPPORTED, "scaled_termination is not implemented in this build");
+    return set_error(MPCQP_E_UNSUPPORTED, "scaled_termination is not implemented in this build");
   if (s->max_iter <= 0 || s->alpha <= 0 || s->alpha >= 2 || s->sigma <= 0 || s->rho <= 0 ||
       s->scaling < 0 || s->check_termination < 0 || s->eps_abs < 0 || s->eps_rel < 0)
-    return fail(MPCQP_E_INVALID, "invalid settings");
+    return set_error(MPCQP_E_INVALID, "invalid settings");
   mpcqp_handle* h = new mpcqp_handle();
+  // every failure from here on destroys the handle (msg by value: it may live in the handle)
+  auto fail = [h](int code, std::string msg) { return mpcqp_destroy(h), set_error(code, msg); };
   h->set = *s;
   h->B = batch;
   h->stream = (hipStream_t)stream;
-  if (!plan_for(st, h->plan)) {
-    std::string e = h->plan.error;
-    delete h;
-    return fail(MPCQP_E_UNSUPPORTED, e);
-  }
-  h->block = 64 * h->plan.waves;
+  if (!plan_for(st, h->plan)) return fail(MPCQP_E_UNSUPPORTED, h->plan.error);
   const Plan& pl = h->plan;
-  if (pl.CACC - pl.W != pl.NKP) {  // the kernel addresses C as W + NKP (an immediate offset)
-    delete h;
-    return fail(MPCQP_E_UNSUPPORTED, "internal: accumulator region does not follow the solve vector");
-  }
-  if (pl.nfac < 1 || pl.nfwd < 1 || pl.nbwd < 1) {
-    delete h;
-    return fail(MPCQP_E_UNSUPPORTED, "internal: empty schedule");
-  }
-  auto cleanup_fail = [&](int code, const std::string& msg) {
-    mpcqp_destroy(h);
-    return fail(code, msg);
-  };
-  {
-    const bool mreg = use_mreg(pl);
-    h->kern = select_kernel(pl.n, pl.m, pl.paired,
-                            pl.waves == 2 ? (pl.split_steps ? 2 : 3) : 1, pl.mat_first, pl.mv_global,
-                            mreg);
-    if (!h->kern) {
-      delete h;
-      return fail(MPCQP_E_UNSUPPORTED, "problem dimensions exceed the instantiated kernels");
-    }
-    // structure blob
-    std::vector<char> blob;
-    size_t o_fac = 0, o_tail = 0, o_fwd = 0, o_bwd = 0;
-    push_chain(blob, pl.fac, pl.tail, FAC_STEP_WORDS, o_fac, o_tail);
-    push_chain(blob, pl.fwd, pl.bwd, SOLVE_STEP_WORDS, o_fwd, o_bwd);
-    size_t o_Lc = push_blob(blob, pl.Lcol), o_sP = push_blob(blob, pl.slotP),
-           o_sA = push_blob(blob, pl.slotA), o_sR = push_blob(blob, pl.slotRho),
-           o_sS = push_blob(blob, pl.slotSig), o_wx = push_blob(blob, pl.wsx),
-           o_wz = push_blob(blob, pl.wsz), o_Ap = push_blob(blob, pl.Ap), o_Ai = push_blob(blob, pl.Ai),
-           o_Ac = push_blob(blob, pl.Acol), o_Arp = push_blob(blob, pl.Arp),
-           o_Ark = push_blob(blob, pl.Ark), o_Arj = push_blob(blob, pl.Arj),
-           o_Pi = push_blob(blob, pl.Pi), o_Pc = push_blob(blob, pl.Pcol),
-           o_Psp = push_blob(blob, pl.Psp), o_Psk = push_blob(blob, pl.Psk),
-           o_Pso = push_blob(blob, pl.Pso), o_eAs = push_blob(blob, pl.ellA.src),
-           o_eAi = push_blob(blob, pl.ellA.in), o_eTs = push_blob(blob, pl.ellAt.src),
-           o_eTi = push_blob(blob, pl.ellAt.in), o_ePs = push_blob(blob, pl.ellP.src),
-           o_ePi = push_blob(blob, pl.ellP.in),
-           o_eAv = push_blob(blob, pl.ellA.vpos), o_eTv = push_blob(blob, pl.ellAt.vpos),
-           o_ePv = push_blob(blob, pl.ellP.vpos), o_eAk = push_blob(blob, pl.ellA.pk),
-           o_eTk = push_blob(blob, pl.ellAt.pk), o_ePk = push_blob(blob, pl.ellP.pk),
-           o_eAq = push_blob(blob, pl.ellA.sk), o_eTq = push_blob(blob, pl.ellAt.sk),
-           o_ePq = push_blob(blob, pl.ellP.sk), o_sra = push_blob(blob, pl.sra),
-           o_sca = push_blob(blob, pl.sca), o_wc = push_blob(blob, pl.wcopy),
-           o_bc = push_blob(blob, pl.bcopy);
-    std::vector<uint32_t> fwdc, fwdm, bwdc, bwdm;
-    if (mreg) {
-      split_records(pl, pl.fwd, pl.nfwd, fwdc, fwdm);
-      split_records(pl, pl.bwd, pl.nbwd, bwdc, bwdm);
-    }
-    const size_t o_fwdc = push_table(blob, fwdc, SOLVEC_STEP_WORDS), o_fwdm = push_blob(blob, fwdm),
-                 o_bwdc = push_table(blob, bwdc, SOLVEC_STEP_WORDS), o_bwdm = push_blob(blob, bwdm);
-    if (hipMalloc(&h->d_blob, blob.size()) != hipSuccess)
-      return cleanup_fail(MPCQP_E_HIP, "hipMalloc(structure)");
-    if (hipMemcpy(h->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess)
-      return cleanup_fail(MPCQP_E_HIP, "hipMemcpy(structure)");
-    char* b = h->d_blob;
-    DevPlan& dp = h->dp;
-    dp.fac = (const uint32_t*)(b + o_fac), dp.tail = (const uint32_t*)(b + o_tail);
-    dp.fwd = (const uint32_t*)(b + o_fwd), dp.bwd = (const uint32_t*)(b + o_bwd);
-    dp.nfac = pl.nfac, dp.ntail = pl.ntail, dp.nfwd = pl.nfwd, dp.nbwd = pl.nbwd;
-    dp.fwdc = (const uint32_t*)(b + o_fwdc), dp.fwdm = (const uint32_t*)(b + o_fwdm);
-    dp.bwdc = (const uint32_t*)(b + o_bwdc), dp.bwdm = (const uint32_t*)(b + o_bwdm);
-    dp.Lcol = (const uint16_t*)(b + o_Lc);
-    dp.slotP = (const uint16_t*)(b + o_sP), dp.slotA = (const uint16_t*)(b + o_sA);
-    dp.slotRho = (const uint16_t*)(b + o_sR), dp.slotSig = (const uint16_t*)(b + o_sS);
-    dp.wsx = (const uint16_t*)(b + o_wx), dp.wsz = (const uint16_t*)(b + o_wz);
-    dp.wcopy = (const uint32_t*)(b + o_wc);
-    dp.bcopy = (const uint32_t*)(b + o_bc);
-    dp.Ap = (const uint16_t*)(b + o_Ap), dp.Ai = (const uint16_t*)(b + o_Ai);
-    dp.Acol = (const uint16_t*)(b + o_Ac), dp.Arp = (const uint16_t*)(b + o_Arp);
-    dp.Ark = (const uint16_t*)(b + o_Ark), dp.Arj = (const uint16_t*)(b + o_Arj);
-    dp.Pi = (const uint16_t*)(b + o_Pi), dp.Pcol = (const uint16_t*)(b + o_Pc);
-    dp.Psp = (const uint16_t*)(b + o_Psp), dp.Psk = (const uint16_t*)(b + o_Psk);
-    dp.Pso = (const uint16_t*)(b + o_Pso);
-    auto ell = [&](const Ell& e, size_t os, size_t oi, size_t ov, size_t ok, size_t oq,
-                   EllDev& d) {
-      d.src = (const uint16_t*)(b + os), d.in = (const uint16_t*)(b + oi), d.total = e.total;
-      d.vpos = (const uint16_t*)(b + ov), d.pk = (const uint32_t*)(b + ok);
-      d.sk = (const uint16_t*)(b + oq);
-      for (int r = 0; r < ELL_MAXR; ++r) d.K[r] = e.K[r], d.off[r] = e.off[r];
-      d.nlong = e.nlong;
-      for (int q = 0; q < ELL_MAXLONG; ++q)
-        d.long_out[q] = e.long_out[q], d.long_off[q] = e.long_off[q], d.long_cnt[q] = e.long_cnt[q];
-    };
-    ell(pl.ellA, o_eAs, o_eAi, o_eAv, o_eAk, o_eAq, dp.eA);
-    ell(pl.ellAt, o_eTs, o_eTi, o_eTv, o_eTk, o_eTq, dp.eAt);
-    ell(pl.ellP, o_ePs, o_ePi, o_ePv, o_ePk, o_ePq, dp.eP);
-    dp.inst_doubles = (pl.LDS_N + 1) & ~1;
-    dp.n = pl.n, dp.m = pl.m, dp.nk = pl.nk, dp.nnzP = pl.nnzP, dp.nnzA = pl.nnzA;
-    dp.nnzL = pl.nnzL;
-    dp.LX = pl.LX, dp.DINV = pl.DINV, dp.W = pl.W, dp.CACC = pl.CACC, dp.ZERO = pl.ZERO;
-    dp.ONE = pl.ONE, dp.MONE = pl.MONE, dp.LDS_N = pl.LDS_N, dp.NKS = pl.NKP / 64;
-    dp.S_P = pl.S_P, dp.S_A = pl.S_A, dp.S_DT = pl.S_DT, dp.S_ET = pl.S_ET;
-    dp.S_ZERO = pl.S_ZERO;
-    dp.MV = pl.MV, dp.MVZ = pl.MVZ, dp.mv_slab = pl.mv_slab;
-    dp.sra = (const uint16_t*)(b + o_sra), dp.sca = (const uint16_t*)(b + o_sca), dp.SJ = pl.SJ;
-    dp.XCH = pl.XCH, dp.XID = pl.XID;
-    // the vector passes address C through W's slot plus the compile-time distance 64 (RN + RM)
-    if (pl.CACC - pl.W != pl.NKP || pl.NKP != 64 * (pl.RN + pl.RM))
-      return cleanup_fail(MPCQP_E_INVALID, "internal: C region not at the kernel's distance from W");
-    if (pl.SJ > 8 * pl.RN)  // the kernel holds 8 RN row / column slots per lane (scale_problem)
-      return cleanup_fail(MPCQP_E_UNSUPPORTED, "too many matrix values for the scaling registers");
-    // the sequential sums stage their terms in the accumulator region C (NKP doubles, free during
-    // the checks): a long mat-vec output's products per wave, the certificates' n / m terms
-    for (const Ell* e : {&pl.ellA, &pl.ellAt, &pl.ellP}) {
-      int tot = 0;  // a mat-vec stages all its long outputs at once (ell_apply)
-      for (int L = 0; L < e->nlong; ++L) tot += e->long_cnt[L];
-      if (tot > pl.NKP / pl.waves)
-        return cleanup_fail(MPCQP_E_UNSUPPORTED, "internal: long mat-vec outputs exceed their staging");
-    }
+  h->block = 64 * pl.waves;
 
-    // occupancy (LDS image and VGPRs) -> persistent grid
-    int dev = 0, ncu = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return cleanup_fail(MPCQP_E_HIP, "hipGetDevice");
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return cleanup_fail(MPCQP_E_HIP, "hipDeviceGetAttribute");
-    const int inst_bytes = dp.inst_doubles * 8;
-    const int lds_cap = 160 * 1024;
-    // diagnostic: MPCQP_LDS_PAD extra bytes per workgroup (occupancy scans; never set in product)
-    const int lds_alloc = inst_bytes + std::max(0, env_int("MPCQP_LDS_PAD", 0));
-    if (lds_alloc > lds_cap)
-      return cleanup_fail(MPCQP_E_UNSUPPORTED, "instance image exceeds the LDS of a CU");
-    if (hipFuncSetAttribute((const void*)h->kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            lds_cap) != hipSuccess)
-      return cleanup_fail(MPCQP_E_HIP, "hipFuncSetAttribute");
-    // register / scratch guard: builds above ~440 registers computed wrong
-    // iterates from a wave's second instance on (High-register builds); a product kernel
-    // beyond the validated budget is refused instead of launched (diagnostic builds may raise it)
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, (const void*)h->kern) != hipSuccess)
-      return cleanup_fail(MPCQP_E_HIP, "hipFuncGetAttributes");
-    h->kregs = fa.numRegs;
-    h->kscratch = (int)fa.localSizeBytes;
-    if (h->kregs > env_int("MPCQP_REG_BUDGET", MPCQP_MAX_KERNEL_REGS) ||
-        h->kscratch > MPCQP_MAX_KERNEL_SCRATCH)
-      return cleanup_fail(MPCQP_E_UNSUPPORTED,
-                          "solve kernel allocates " + std::to_string(h->kregs) + " registers / " +
-                              std::to_string(h->kscratch) +
-                              " scratch bytes per lane: above the validated budget");
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)h->kern, h->block, lds_alloc) !=
-            hipSuccess || nb <= 0)
-      return cleanup_fail(MPCQP_E_UNSUPPORTED, "kernel does not fit on a CU (LDS/VGPR)");
-    h->per_cu = nb;
-    h->waves_per_cu = nb * pl.waves;
-    h->lds_bytes = lds_alloc;
-    h->grid = std::min(batch, nb * ncu);
-  }
-  const size_t Bz = (size_t)batch;
-  bool ok = hipMalloc(&h->Px, sizeof(double) * std::max(1, pl.nnzP)) == hipSuccess &&
-            hipMalloc(&h->q, sizeof(double) * pl.n) == hipSuccess &&
-            hipMalloc(&h->Ax, sizeof(double) * Bz * std::max(1, pl.nnzA)) == hipSuccess &&
-            hipMalloc(&h->l, sizeof(double) * Bz * pl.m) == hipSuccess &&
-            hipMalloc(&h->u, sizeof(double) * Bz * pl.m) == hipSuccess &&
-            hipMalloc(&h->xs, sizeof(double) * Bz * pl.n) == hipSuccess &&
-            hipMalloc(&h->zs, sizeof(double) * Bz * pl.m) == hipSuccess &&
-            hipMalloc(&h->ys, sizeof(double) * Bz * pl.m) == hipSuccess &&
-            hipMalloc(&h->Ecls, sizeof(double) * Bz * pl.m) == hipSuccess &&
-            hipMalloc(&h->Pw, 2 * sizeof(double) * Bz * std::max(1, pl.nnzP)) == hipSuccess &&
-            hipMalloc(&h->qw, 2 * sizeof(double) * Bz * pl.n) == hipSuccess &&
-            hipMalloc(&h->dsel, sizeof(int32_t) * Bz) == hipSuccess &&
-            hipMalloc(&h->pend, sizeof(int32_t) * Bz) == hipSuccess &&
-            hipMalloc(&h->rho, sizeof(double) * Bz) == hipSuccess &&
-            hipMalloc(&h->has_state, sizeof(int32_t) * Bz) == hipSuccess &&
-            hipMalloc(&h->scratch, sizeof(double) * (size_t)h->grid * slab_doubles(pl.n, pl.m, pl.mv_slab)) ==
-                hipSuccess &&
-            hipMalloc(&h->counter, 64) == hipSuccess;
-  if (!ok) return cleanup_fail(MPCQP_E_HIP, "hipMalloc(batch buffers)");
-  if (hipMemset(h->has_state, 0, sizeof(int32_t) * Bz) != hipSuccess ||
-      hipMemsetD32(h->dsel, -2, Bz) != hipSuccess || hipMemset(h->pend, 0, sizeof(int32_t) * Bz) != hipSuccess)
-    return cleanup_fail(MPCQP_E_HIP, "hipMemset");
+  // the device image: laid out and checked on the host (host_abi.cpp), uploaded, dp pointed at it
+  const bool mreg = use_mreg(pl);
+  DevImage img;
+  std::string err;
+  if (int rc = build_dev_image(pl, mreg, img, err)) return fail(rc, err);
+  h->kern = select_kernel(pl.n, pl.m, pl.paired, pl.waves == 2 ? (pl.split_steps ? 2 : 3) : 1,
+                          pl.mat_first, pl.mv_global, mreg);
+  if (!h->kern) return fail(MPCQP_E_UNSUPPORTED, "problem dimensions exceed the instantiated kernels");
+  if (!dev_alloc(h, h->d_blob, img.blob.size())) return fail(MPCQP_E_HIP, "hipMalloc(structure)");
+  if (hipMemcpy(h->d_blob, img.blob.data(), img.blob.size(), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(MPCQP_E_HIP, "hipMemcpy(structure)");
+  rebase(img, h->d_blob);
+  h->dp = img.dp;
+
+  // occupancy (LDS image and VGPRs) -> persistent grid
+  int dev = 0, ncu = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return fail(MPCQP_E_HIP, "hipGetDevice");
+  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return fail(MPCQP_E_HIP, "hipDeviceGetAttribute");
+  const int inst_bytes = h->dp.inst_doubles * 8;
+  const int lds_cap = 160 * 1024;
+  // diagnostic: MPCQP_LDS_PAD extra bytes per workgroup (occupancy scans; never set in product)
+  const int lds_alloc = inst_bytes + std::max(0, diag_env_int("MPCQP_LDS_PAD", 0));
+  if (lds_alloc > lds_cap) return fail(MPCQP_E_UNSUPPORTED, "instance image exceeds the LDS of a CU");
+  if (hipFuncSetAttribute((const void*)h->kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                          lds_cap) != hipSuccess)
+    return fail(MPCQP_E_HIP, "hipFuncSetAttribute");
+  // register / scratch guard: builds above ~440 registers computed wrong
+  // iterates from a wave's second instance on (High-register builds); a product kernel
+  // beyond the validated budget is refused instead of launched (diagnostic builds may raise it)
+  hipFuncAttributes fa{};
+  if (hipFuncGetAttributes(&fa, (const void*)h->kern) != hipSuccess)
+    return fail(MPCQP_E_HIP, "hipFuncGetAttributes");
+  h->kregs = fa.numRegs;
+  h->kscratch = (int)fa.localSizeBytes;
+  if (h->kregs > diag_env_int("MPCQP_REG_BUDGET", MPCQP_MAX_KERNEL_REGS) ||
+      h->kscratch > MPCQP_MAX_KERNEL_SCRATCH)
+    return fail(MPCQP_E_UNSUPPORTED,
+                "solve kernel allocates " + std::to_string(h->kregs) + " registers / " +
+                    std::to_string(h->kscratch) + " scratch bytes per lane: above the validated budget");
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)h->kern, h->block, lds_alloc) !=
+          hipSuccess || nb <= 0)
+    return fail(MPCQP_E_UNSUPPORTED, "kernel does not fit on a CU (LDS/VGPR)");
+  h->per_cu = nb;
+  h->waves_per_cu = nb * pl.waves;
+  h->lds_bytes = lds_alloc;
+  h->grid = std::min(batch, nb * ncu);
+
+  const size_t Bz = (size_t)batch, D = sizeof(double), I = sizeof(int32_t);
+  const size_t nP = (size_t)std::max(1, pl.nnzP), nA = (size_t)std::max(1, pl.nnzA);
+  const bool ok = dev_alloc(h, h->Px, D * nP) && dev_alloc(h, h->q, D * pl.n) &&
+                  dev_alloc(h, h->Ax, D * Bz * nA) && dev_alloc(h, h->l, D * Bz * pl.m) &&
+                  dev_alloc(h, h->u, D * Bz * pl.m) && dev_alloc(h, h->xs, D * Bz * pl.n) &&
+                  dev_alloc(h, h->zs, D * Bz * pl.m) && dev_alloc(h, h->ys, D * Bz * pl.m) &&
+                  dev_alloc(h, h->Ecls, D * Bz * pl.m) && dev_alloc(h, h->Pw, 2 * D * Bz * nP) &&
+                  dev_alloc(h, h->qw, 2 * D * Bz * pl.n) && dev_alloc(h, h->dsel, I * Bz) &&
+                  dev_alloc(h, h->pend, I * Bz) && dev_alloc(h, h->rho, D * Bz) &&
+                  dev_alloc(h, h->has_state, I * Bz) &&
+                  dev_alloc(h, h->scratch, D * (size_t)h->grid * slab_doubles(pl.n, pl.m, pl.mv_slab)) &&
+                  dev_alloc(h, h->counter, 64);
+  if (!ok) return fail(MPCQP_E_HIP, "hipMalloc(batch buffers)");
+  if (hipMemset(h->has_state, 0, I * Bz) != hipSuccess || hipMemsetD32(h->dsel, -2, Bz) != hipSuccess ||
+      hipMemset(h->pend, 0, I * Bz) != hipSuccess)
+    return fail(MPCQP_E_HIP, "hipMemset");
   *out = h;
   return 0;
 }
 
 int mpcqp_destroy(mpcqp_handle* h) {
   if (!h) return 0;
-  void* bufs[] = {h->d_blob, h->Px, h->q,    h->Ax,        h->l,       h->u,      h->xs,
-                  h->zs,     h->ys, h->Ecls, h->rho, h->has_state, h->scratch, h->counter,
-                  h->Pw,     h->qw, h->dsel, h->pend, h->PxB, h->qB};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
+  for (void* p : h->owned) (void)hipFree(p);
   delete h;
   return 0;
 }
 
-// every instance's drift buffer row <- src (device), on the handle's stream
+// every instance's row of dst <- the one row src (device), on the handle's stream
 static hipError_t bcast_rows(mpcqp_handle* h, double* dst, const double* src, int cnt) {
-  const size_t tot = (size_t)h->B * cnt;
-  if (tot == 0) return hipSuccess;
-  hipLaunchKernelGGL(bcast_rows_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream,
-                     dst, src, h->B, cnt);
-  return hipGetLastError();
-}
-
-int mpcqp_set_data(mpcqp_handle* h, const double* Px, const double* q, const double* Ax,
-                   const double* l, const double* u) {
-  if (!h || !Px || !q || !Ax || !l || !u) return fail(MPCQP_E_INVALID, "null argument");
-  const Plan& pl = h->plan;
-  const size_t B = (size_t)h->B;
-  HIPCHK(hipMemcpyAsync(h->Px, Px, sizeof(double) * pl.nnzP, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->q, q, sizeof(double) * pl.n, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->Ax, Ax, sizeof(double) * B * pl.nnzA, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->l, l, sizeof(double) * B * pl.m, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->u, u, sizeof(double) * B * pl.m, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemsetAsync(h->has_state, 0, sizeof(int32_t) * B, h->stream));
-  // a new setup: the next solve scales the given data (drift_of), no update of A pending
-  HIPCHK(hipMemsetD32Async(h->dsel, -2, B, h->stream));
-  HIPCHK(hipMemsetAsync(h->pend, 0, sizeof(int32_t) * B, h->stream));
-  h->has_data = true;
-  h->batched = false;  // the shared set-up row again (KParams stride 0)
-  return 0;
+  return launch_1d(h, bcast_rows_kernel, (size_t)h->B * cnt, dst, src, h->B, cnt);
 }
 
 // the per-instance set-up buffers, allocated at the first batched call
 static int batched_rows(mpcqp_handle* h) {
   const size_t B = (size_t)h->B;
-  if (!h->PxB) HIPCHK(hipMalloc(&h->PxB, sizeof(double) * B * std::max(1, h->plan.nnzP)));
-  if (!h->qB) HIPCHK(hipMalloc(&h->qB, sizeof(double) * B * h->plan.n));
+  if ((!h->PxB && !dev_alloc(h, h->PxB, sizeof(double) * B * std::max(1, h->plan.nnzP))) ||
+      (!h->qB && !dev_alloc(h, h->qB, sizeof(double) * B * h->plan.n)))
+    return set_error(MPCQP_E_HIP, "hipMalloc(per-instance cost rows)");
   return 0;
 }
 // a handle with shared set-up data moves to per-instance rows holding the same values
@@ -2491,118 +2299,118 @@ static int promote(mpcqp_handle* h) {
   return 0;
 }
 
-int mpcqp_set_data_batched(mpcqp_handle* h, const double* Px, const double* q, const double* Ax,
-                           const double* l, const double* u) {
-  if (!h || !Px || !q || !Ax || !l || !u) return fail(MPCQP_E_INVALID, "null argument");
-  if (int rc = batched_rows(h)) return rc;
+// mpcqp_set_data (one P / q row for every instance) and mpcqp_set_data_batched (a row each)
+static int set_data(mpcqp_handle* h, bool batched, const double* Px, const double* q,
+                    const double* Ax, const double* l, const double* u) {
+  if (int rc = guard(h, Px && q && Ax && l && u)) return rc;
+  if (int rc = batched ? batched_rows(h) : 0) return rc;
   const Plan& pl = h->plan;
-  const size_t B = (size_t)h->B;
-  HIPCHK(hipMemcpyAsync(h->PxB, Px, sizeof(double) * B * pl.nnzP, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->qB, q, sizeof(double) * B * pl.n, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->Ax, Ax, sizeof(double) * B * pl.nnzA, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->l, l, sizeof(double) * B * pl.m, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->u, u, sizeof(double) * B * pl.m, hipMemcpyDeviceToDevice, h->stream));
+  const size_t B = (size_t)h->B, rows = batched ? B : 1;
+  const SetupRows to = setup_rows(h, batched);
+  HIPCHK(copy_rows(h, to.Px, Px, rows * pl.nnzP));
+  HIPCHK(copy_rows(h, to.q, q, rows * pl.n));
+  HIPCHK(copy_rows(h, h->Ax, Ax, B * pl.nnzA));
+  HIPCHK(copy_rows(h, h->l, l, B * pl.m));
+  HIPCHK(copy_rows(h, h->u, u, B * pl.m));
   HIPCHK(hipMemsetAsync(h->has_state, 0, sizeof(int32_t) * B, h->stream));
+  // a new setup: the next solve scales the given data (drift_of), no update of A pending
   HIPCHK(hipMemsetD32Async(h->dsel, -2, B, h->stream));
   HIPCHK(hipMemsetAsync(h->pend, 0, sizeof(int32_t) * B, h->stream));
   h->has_data = true;
-  h->batched = true;
+  h->batched = batched;  // plain: the shared set-up row again (KParams stride 0)
   return 0;
 }
 
+int mpcqp_set_data(mpcqp_handle* h, const double* Px, const double* q, const double* Ax,
+                   const double* l, const double* u) {
+  return set_data(h, false, Px, q, Ax, l, u);
+}
+
+int mpcqp_set_data_batched(mpcqp_handle* h, const double* Px, const double* q, const double* Ax,
+                           const double* l, const double* u) {
+  return set_data(h, true, Px, q, Ax, l, u);
+}
+
 int mpcqp_update_bounds(mpcqp_handle* h, const double* l, const double* u) {
-  if (!h || !l || !u) return fail(MPCQP_E_INVALID, "null argument");
-  if (!h->has_data) return fail(MPCQP_E_NODATA, "update before set_data");
-  const size_t B = (size_t)h->B;
-  HIPCHK(hipMemcpyAsync(h->l, l, sizeof(double) * B * h->plan.m, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->u, u, sizeof(double) * B * h->plan.m, hipMemcpyDeviceToDevice, h->stream));
+  if (int rc = guard(h, l && u, "update")) return rc;
+  const size_t Bm = (size_t)h->B * h->plan.m;
+  HIPCHK(copy_rows(h, h->l, l, Bm));
+  HIPCHK(copy_rows(h, h->u, u, Bm));
   return 0;
 }
 
 int mpcqp_update_A(mpcqp_handle* h, const double* Ax) {
-  if (!h || !Ax) return fail(MPCQP_E_INVALID, "null argument");
-  if (!h->has_data) return fail(MPCQP_E_NODATA, "update before set_data");
-  HIPCHK(hipMemcpyAsync(h->Ax, Ax, sizeof(double) * (size_t)h->B * h->plan.nnzA,
-                        hipMemcpyDeviceToDevice, h->stream));
+  if (int rc = guard(h, Ax, "update")) return rc;
+  HIPCHK(copy_rows(h, h->Ax, Ax, (size_t)h->B * h->plan.nnzA));
   // each instance's next solve follows osqp_update_A (unscale, overwrite, rescale: drift_of)
   HIPCHK(hipMemsetD32Async(h->pend, 1, (size_t)h->B, h->stream));
   return 0;
 }
 
 int mpcqp_update_lin_cost(mpcqp_handle* h, const double* q) {
-  if (!h || !q) return fail(MPCQP_E_INVALID, "null argument");
-  if (!h->has_data) return fail(MPCQP_E_NODATA, "update before set_data");
-  HIPCHK(hipMemcpyAsync(h->q, q, sizeof(double) * h->plan.n, hipMemcpyDeviceToDevice, h->stream));
-  if (h->batched) HIPCHK(bcast_rows(h, h->qB, h->q, h->plan.n));
+  if (int rc = guard(h, q, "update")) return rc;
+  const int n = h->plan.n;
+  HIPCHK(copy_rows(h, h->q, q, n));
+  if (h->batched) HIPCHK(bcast_rows(h, h->qB, h->q, n));
   // the next solve rescales the new q itself (OSQP would carry (q D) c unscaled: an ulp apart; the
   // reference never updates q): both drift buffers, whichever drift_of picks
-  HIPCHK(bcast_rows(h, h->qw, h->q, h->plan.n));
-  HIPCHK(bcast_rows(h, h->qw + (size_t)h->B * h->plan.n, h->q, h->plan.n));
+  HIPCHK(bcast_rows(h, h->qw, h->q, n));
+  HIPCHK(bcast_rows(h, h->qw + (size_t)h->B * n, h->q, n));
   return 0;
 }
 
 int mpcqp_update_lin_cost_batched(mpcqp_handle* h, const double* q) {
-  if (!h || !q) return fail(MPCQP_E_INVALID, "null argument");
-  if (!h->has_data) return fail(MPCQP_E_NODATA, "update before set_data");
+  if (int rc = guard(h, q, "update")) return rc;
   if (int rc = promote(h)) return rc;
   // as mpcqp_update_lin_cost, row for row: the set-up q and both drift buffers
-  const size_t bytes = sizeof(double) * (size_t)h->B * h->plan.n;
-  HIPCHK(hipMemcpyAsync(h->qB, q, bytes, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->qw, q, bytes, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->qw + (size_t)h->B * h->plan.n, q, bytes, hipMemcpyDeviceToDevice,
-                        h->stream));
+  const size_t Bn = (size_t)h->B * h->plan.n;
+  HIPCHK(copy_rows(h, h->qB, q, Bn));
+  HIPCHK(copy_rows(h, h->qw, q, Bn));
+  HIPCHK(copy_rows(h, h->qw + Bn, q, Bn));
   return 0;
 }
 
 // osqp_update_P for every instance (update_P_kernel): src_stride 0 = one row for all
 static int update_P(mpcqp_handle* h, const double* Px, int src_stride) {
   const int cnt = h->plan.nnzP;
-  const size_t tot = (size_t)h->B * cnt;
-  if (tot == 0) return 0;
-  hipLaunchKernelGGL(update_P_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream,
-                     h->batched ? h->PxB : h->Px, h->batched ? cnt : 0, h->Pw, Px, src_stride,
-                     h->dsel, h->pend, h->B, cnt);
-  HIPCHK(hipGetLastError());
+  const SetupRows s = setup_rows(h, h->batched);
+  HIPCHK(launch_1d(h, update_P_kernel, (size_t)h->B * cnt, s.Px, s.Px_stride, h->Pw, Px, src_stride,
+                   h->dsel, h->pend, h->B, cnt));
   return 0;
 }
 
 int mpcqp_update_P(mpcqp_handle* h, const double* Px) {
-  if (!h || !Px) return fail(MPCQP_E_INVALID, "null argument");
-  if (!h->has_data) return fail(MPCQP_E_NODATA, "update before set_data");
+  if (int rc = guard(h, Px, "update")) return rc;
   return update_P(h, Px, 0);
 }
 
 int mpcqp_update_P_batched(mpcqp_handle* h, const double* Px) {
-  if (!h || !Px) return fail(MPCQP_E_INVALID, "null argument");
-  if (!h->has_data) return fail(MPCQP_E_NODATA, "update before set_data");
+  if (int rc = guard(h, Px, "update")) return rc;
   if (int rc = promote(h)) return rc;
   return update_P(h, Px, h->plan.nnzP);
 }
 
 int mpcqp_warm_start(mpcqp_handle* h, const double* x, const double* y) {
-  if (!h || !x || !y) return fail(MPCQP_E_INVALID, "null argument");
-  if (!h->has_data) return fail(MPCQP_E_NODATA, "warm start before set_data");
+  if (int rc = guard(h, x && y, "warm start")) return rc;
   const size_t B = (size_t)h->B;
-  HIPCHK(hipMemcpyAsync(h->xs, x, sizeof(double) * B * h->plan.n, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->ys, y, sizeof(double) * B * h->plan.m, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(copy_rows(h, h->xs, x, B * h->plan.n));
+  HIPCHK(copy_rows(h, h->ys, y, B * h->plan.m));
   // has_state = 2 for every instance, but keep rho: a warm start does not reset rho in OSQP.
   // (rho_state is only read when has_state != 0; instances never solved start from settings.rho)
-  std::vector<int32_t> two(B, 2);
-  HIPCHK(hipMemcpyAsync(h->has_state, two.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice,
-                        h->stream));
+  HIPCHK(hipMemsetD32Async(h->has_state, 2, B, h->stream));
+  // the caller's x and y may be temporaries freed on return (BatchQP.warm_start)
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
 
 int mpcqp_solve(mpcqp_handle* h, double* x, double* y, const mpcqp_info* info) {
-  if (!h) return fail(MPCQP_E_INVALID, "null handle");
-  if (!h->has_data) return fail(MPCQP_E_NODATA, "solve before set_data");
+  if (int rc = guard(h, true, "solve")) return rc;
+  const SetupRows s = setup_rows(h, h->batched);
   KParams p{};
   p.pl = h->dp;
   p.s = h->set;
   p.B = h->B;
-  p.Px = h->batched ? h->PxB : h->Px, p.q = h->batched ? h->qB : h->q;
-  p.Px_stride = h->batched ? h->plan.nnzP : 0, p.q_stride = h->batched ? h->plan.n : 0;
+  p.Px = s.Px, p.q = s.q, p.Px_stride = s.Px_stride, p.q_stride = s.q_stride;
   p.Ax = h->Ax, p.l = h->l, p.u = h->u;
   p.xs = h->xs, p.zs = h->zs, p.ys = h->ys, p.rho_state = h->rho, p.Ecls = h->Ecls;
   p.Pw = h->Pw, p.qw = h->qw;
@@ -2625,7 +2433,7 @@ int mpcqp_solve(mpcqp_handle* h, double* x, double* y, const mpcqp_info* info) {
 #ifdef MPCQP_TIMING
 // diagnostic builds only (not part of include/mpcqp.h): device buffer of T_NSLOT uint64 counters
 int mpcqp_debug_timing(mpcqp_handle* h, unsigned long long* dev_buf) {
-  if (!h) return fail(MPCQP_E_INVALID, "null handle");
+  if (int rc = guard(h)) return rc;
   h->timing = dev_buf;
   return 0;
 }
@@ -2640,7 +2448,7 @@ int mpcqp_debug_pair_inject(int on) {
 #endif
 
 int mpcqp_data_buffers(mpcqp_handle* h, double** Ax, double** l, double** u) {
-  if (!h) return fail(MPCQP_E_INVALID, "null handle");
+  if (int rc = guard(h)) return rc;
   // the caller may rewrite A in place between solves: every later solve follows an update of A
   if (Ax) h->a_inplace = true;
   if (Ax) *Ax = h->Ax;
@@ -2650,82 +2458,71 @@ int mpcqp_data_buffers(mpcqp_handle* h, double** Ax, double** l, double** u) {
 }
 
 int mpcqp_copy_data(mpcqp_handle* h, double* Ax, double* l, double* u) {
-  if (!h) return fail(MPCQP_E_INVALID, "null handle");
+  if (int rc = guard(h)) return rc;
   const size_t B = (size_t)h->B;
-  if (Ax)
-    HIPCHK(hipMemcpyAsync(Ax, h->Ax, sizeof(double) * B * h->plan.nnzA, hipMemcpyDeviceToDevice,
-                          h->stream));
-  if (l)
-    HIPCHK(hipMemcpyAsync(l, h->l, sizeof(double) * B * h->plan.m, hipMemcpyDeviceToDevice,
-                          h->stream));
-  if (u)
-    HIPCHK(hipMemcpyAsync(u, h->u, sizeof(double) * B * h->plan.m, hipMemcpyDeviceToDevice,
-                          h->stream));
+  if (Ax) HIPCHK(copy_rows(h, Ax, h->Ax, B * h->plan.nnzA));
+  if (l) HIPCHK(copy_rows(h, l, h->l, B * h->plan.m));
+  if (u) HIPCHK(copy_rows(h, u, h->u, B * h->plan.m));
   return 0;
 }
 
 int mpcqp_set_skip(mpcqp_handle* h, const int32_t* skip) {
-  if (!h) return fail(MPCQP_E_INVALID, "null handle");
+  if (int rc = guard(h)) return rc;
   h->skip = skip;
   return 0;
 }
 
 int mpcqp_set_order(mpcqp_handle* h, const int32_t* order) {
-  if (!h) return fail(MPCQP_E_INVALID, "null handle");
+  if (int rc = guard(h)) return rc;
   h->order = order;
   return 0;
 }
 
 int mpcqp_get_state(const mpcqp_handle* h, double* xs, double* zs, double* ys, double* rho,
                     int32_t* has_state) {
-  if (!h) return fail(MPCQP_E_INVALID, "null handle");
+  if (int rc = guard(h)) return rc;
   const size_t B = (size_t)h->B;
   const Plan& pl = h->plan;
-  if (xs) HIPCHK(hipMemcpyAsync(xs, h->xs, sizeof(double) * B * pl.n, hipMemcpyDeviceToDevice, h->stream));
-  if (zs) HIPCHK(hipMemcpyAsync(zs, h->zs, sizeof(double) * B * pl.m, hipMemcpyDeviceToDevice, h->stream));
-  if (ys) HIPCHK(hipMemcpyAsync(ys, h->ys, sizeof(double) * B * pl.m, hipMemcpyDeviceToDevice, h->stream));
-  if (rho) HIPCHK(hipMemcpyAsync(rho, h->rho, sizeof(double) * B, hipMemcpyDeviceToDevice, h->stream));
-  if (has_state)
-    HIPCHK(hipMemcpyAsync(has_state, h->has_state, sizeof(int32_t) * B, hipMemcpyDeviceToDevice,
-                          h->stream));
+  if (xs) HIPCHK(copy_rows(h, xs, h->xs, B * pl.n));
+  if (zs) HIPCHK(copy_rows(h, zs, h->zs, B * pl.m));
+  if (ys) HIPCHK(copy_rows(h, ys, h->ys, B * pl.m));
+  if (rho) HIPCHK(copy_rows(h, rho, h->rho, B));
+  if (has_state) HIPCHK(copy_rows(h, has_state, h->has_state, B));
   return 0;
 }
 
 int mpcqp_set_state(mpcqp_handle* h, const double* xs, const double* zs, const double* ys,
                     const double* rho, const int32_t* has_state) {
-  if (!h || !xs || !zs || !ys || !rho || !has_state) return fail(MPCQP_E_INVALID, "null argument");
+  if (int rc = guard(h, xs && zs && ys && rho && has_state)) return rc;
   const size_t B = (size_t)h->B;
   const Plan& pl = h->plan;
-  HIPCHK(hipMemcpyAsync(h->xs, xs, sizeof(double) * B * pl.n, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->zs, zs, sizeof(double) * B * pl.m, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->ys, ys, sizeof(double) * B * pl.m, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->rho, rho, sizeof(double) * B, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->has_state, has_state, sizeof(int32_t) * B, hipMemcpyDeviceToDevice,
-                        h->stream));
+  HIPCHK(copy_rows(h, h->xs, xs, B * pl.n));
+  HIPCHK(copy_rows(h, h->zs, zs, B * pl.m));
+  HIPCHK(copy_rows(h, h->ys, ys, B * pl.m));
+  HIPCHK(copy_rows(h, h->rho, rho, B));
+  HIPCHK(copy_rows(h, h->has_state, has_state, B));
   return 0;
 }
 
 int mpcqp_get_scaling(const mpcqp_handle* h, double* E, double* Pu, double* qu) {
-  if (!h) return fail(MPCQP_E_INVALID, "null handle");
+  if (int rc = guard(h)) return rc;
   const size_t B = (size_t)h->B;
   const Plan& pl = h->plan;
-  if (E) HIPCHK(hipMemcpyAsync(E, h->Ecls, sizeof(double) * B * pl.m, hipMemcpyDeviceToDevice, h->stream));
+  if (E) HIPCHK(copy_rows(h, E, h->Ecls, B * pl.m));
   // the set-up rows of a batched handle are per instance (KParams::Px_stride / q_stride)
-  auto gather = [&](double* dst, const double* W, const double* setup, int cnt) {
-    const size_t tot = B * (size_t)cnt;
-    if (tot == 0) return hipSuccess;
-    hipLaunchKernelGGL(drift_gather_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
-                       h->stream, dst, W, setup, h->batched ? cnt : 0, h->dsel, (int)B, cnt);
-    return hipGetLastError();
-  };
-  if (Pu) HIPCHK(gather(Pu, h->Pw, h->batched ? h->PxB : h->Px, pl.nnzP));
-  if (qu) HIPCHK(gather(qu, h->qw, h->batched ? h->qB : h->q, pl.n));
+  const SetupRows s = setup_rows(h, h->batched);
+  if (Pu)
+    HIPCHK(launch_1d(h, drift_gather_kernel, B * pl.nnzP, Pu, h->Pw, s.Px, s.Px_stride, h->dsel,
+                     h->B, pl.nnzP));
+  if (qu)
+    HIPCHK(launch_1d(h, drift_gather_kernel, B * pl.n, qu, h->qw, s.q, s.q_stride, h->dsel, h->B,
+                     pl.n));
   return 0;
 }
 
 int mpcqp_dims(const mpcqp_handle* h, int32_t* n, int32_t* m, int32_t* nnzP, int32_t* nnzA,
                int32_t* nnzL) {
-  if (!h) return fail(MPCQP_E_INVALID, "null handle");
+  if (int rc = guard(h)) return rc;
   if (n) *n = h->plan.n;
   if (m) *m = h->plan.m;
   if (nnzP) *nnzP = h->plan.nnzP;
@@ -2736,7 +2533,7 @@ int mpcqp_dims(const mpcqp_handle* h, int32_t* n, int32_t* m, int32_t* nnzP, int
 
 int mpcqp_schedule_info(const mpcqp_handle* h, int32_t* fac, int32_t* fwd, int32_t* bwd,
                         int32_t* lds, int32_t* wpc) {
-  if (!h) return fail(MPCQP_E_INVALID, "null handle");
+  if (int rc = guard(h)) return rc;
   if (fac) *fac = (int32_t)(h->plan.nfac + h->plan.ntail);
   if (fwd) *fwd = (int32_t)h->plan.nfwd;
   if (bwd) *bwd = (int32_t)h->plan.nbwd;
@@ -2746,14 +2543,14 @@ int mpcqp_schedule_info(const mpcqp_handle* h, int32_t* fac, int32_t* fwd, int32
 }
 
 int mpcqp_schedule_kind(const mpcqp_handle* h, int32_t* atomics_per_step) {
-  if (!h || !atomics_per_step) return fail(MPCQP_E_INVALID, "null argument");
+  if (int rc = guard(h, atomics_per_step)) return rc;
   *atomics_per_step = h->plan.paired ? 3 : 4;
   return 0;
 }
 
 int mpcqp_kernel_info(const mpcqp_handle* h, int32_t* waves_per_instance, int32_t* instances_per_cu,
                       int32_t* regs, int32_t* scratch_bytes) {
-  if (!h) return fail(MPCQP_E_INVALID, "null handle");
+  if (int rc = guard(h)) return rc;
   if (waves_per_instance) *waves_per_instance = h->plan.waves;
   if (instances_per_cu) *instances_per_cu = h->per_cu;
   if (regs) *regs = h->kregs;
@@ -2762,13 +2559,13 @@ int mpcqp_kernel_info(const mpcqp_handle* h, int32_t* waves_per_instance, int32_
 }
 
 int mpcqp_engine_kind(const mpcqp_handle* h, int32_t* kind) {
-  if (!h || !kind) return fail(MPCQP_E_INVALID, "null argument");
+  if (int rc = guard(h, kind)) return rc;
   *kind = MPCQP_ENGINE_KKT;
   return 0;
 }
 
 int mpcqp_export_symbolic(const mpcqp_handle* h, int32_t* perm, int32_t* Lp, int32_t* Li) {
-  if (!h) return fail(MPCQP_E_INVALID, "null handle");
+  if (int rc = guard(h)) return rc;
   const Plan& pl = h->plan;
   if (perm) std::copy(pl.perm.begin(), pl.perm.end(), perm);
   if (Lp) std::copy(pl.Lp.begin(), pl.Lp.end(), Lp);

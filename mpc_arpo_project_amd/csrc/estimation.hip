@@ -16,8 +16,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <string>
 
 #include "../../include/mpcqp_estimation.h"
+#include "host_abi.hpp"
 #include "plant_dev.hpp"
 
 namespace {
@@ -245,6 +247,11 @@ __global__ void __launch_bounds__(64) plant_rk45_kernel(PlantConsts c, int B, do
   if (failed && !ok) failed[b] = 1;
 }
 
+int launched(const char* entry) {  // the return code of an entry point that has launched its kernel
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : set_error(MPCQP_E_HIP, std::string(entry) + ": " + hipGetErrorString(e));
+}
+
 }  // namespace
 
 struct mpcqp_ukf {
@@ -257,7 +264,7 @@ extern "C" {
 
 int mpcqp_ukf_create(const mpcqp_ukf_model* m, int32_t batch, void* stream, mpcqp_ukf** out) {
 #pragma clang fp contract(off)
-  if (!m || !out || batch <= 0) return -1;
+  if (!m || !out || batch <= 0) return set_error(MPCQP_E_INVALID, "mpcqp_ukf_create: invalid argument");
   *out = nullptr;
   mpcqp_ukf* k = new mpcqp_ukf();
   for (int i = 0; i < 36; ++i) k->c.Ao[i] = m->Ao[i], k->c.Q[i] = m->Q[i];
@@ -290,21 +297,22 @@ int mpcqp_ukf_destroy(mpcqp_ukf* k) {
 
 int mpcqp_ukf_step(mpcqp_ukf* k, double* x, double* P, const double* u, const double* z,
                    const int32_t* active, int32_t* status) {
-  if (!k || !x || !P || !u || !z) return -1;
+  if (!k || !x || !P || !u || !z) return set_error(MPCQP_E_INVALID, "mpcqp_ukf_step: null argument");
   hipLaunchKernelGGL(ukf_step_kernel, dim3((k->B + 63) / 64), dim3(64), 0, k->stream, k->c, k->B,
                      x, P, u, z, active, status);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
+  return launched("mpcqp_ukf_step");
 }
 
 int mpcqp_plant_rk45(const mpcqp_plant_model* m, int32_t batch, void* stream, double* x,
                      const double* u, const double* w, double t0, double dt, int32_t nsub,
                      double* traj, int32_t* failed) {
-  if (!m || !x || !u || batch <= 0 || nsub < 0 || !(dt >= 0.0)) return -1;
+  if (!m || !x || !u || batch <= 0 || nsub < 0 || !(dt >= 0.0))
+    return set_error(MPCQP_E_INVALID, "mpcqp_plant_rk45: invalid argument");
   if (nsub == 0) return 0;
   PlantConsts c{m->two_n, m->m_two_n, m->n2, m->R_T, m->mu, m->g0, m->rtol, m->atol};
   hipLaunchKernelGGL(plant_rk45_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream,
                      c, batch, x, u, w, t0, dt, nsub, traj, failed);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
+  return launched("mpcqp_plant_rk45");
 }
 
 }  // extern "C"
