@@ -51,6 +51,10 @@ struct DevImage {
   std::vector<char> blob;
   DevPlan dp{};
   std::vector<std::pair<size_t, size_t>> fixups;  // byte offset of a pointer in dp, of its table in blob
+  // the solve tables may run as one carried record pipeline (engine.hip RP_CARRY): a one-wave
+  // LDS-operand plan whose forward and backward step counts are multiples of three and whose
+  // look-ahead loads past either table read real steps of the other
+  bool carry = false;
 };
 // Lays out pl's tables (mreg: with the KM_MREG record tables) and checks the plan against what the
 // kernels assume of it: 0, or the MPCQP_E_* code of the failed check with its message in err.

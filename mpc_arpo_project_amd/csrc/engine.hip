@@ -672,6 +672,61 @@ struct SolveOps {
   }
   __device__ __forceinline__ void step(const Rec& r, int) const { solve_step<PAIRED>(r, v); }
 };
+// Record pipelines of the one-wave KM_LDS kernel's ADMM loop.  RP_RESTART: every solve starts with
+// prefetch() and runs run_body -- n + 2 record sets loaded for n steps, the last two never read.
+// RP_CARRY (step counts that are multiples of three): those two sets are steps 0 and 1 of the table
+// that runs next (ImageBuilder::chain lays the tables out as [fwd][bwd][first steps of fwd]), and
+// with n % 3 == 0 the rotation leaves them in sets a and b, where the next solve's steps 0 and 1
+// read them: the pipeline runs on from the forward into the backward solve and, on iterations that
+// neither check nor adapt rho, into the next iteration: n sets are loaded for n steps.
+enum { RP_RESTART = 0, RP_CARRY = 1 };
+// The step loop of a carried pipeline: n % 3 == 0 (checked at plan time), sets a and b hold steps
+// 0 and 1 on entry (in flight); on exit they hold steps n and n + 1 (in flight).  One rotation per
+// trip and one exit.  Every rotation loads its own set c at its top, two steps ahead of its use
+// like every other reload, so set c is no value carried round the back edge, into the loop or out
+// of it.  (Carried, the register allocator kept it in other registers in one solve's loop than in
+// the other's and copied it behind a vmcnt(0), whether its first load stood in front of the loop or
+// under a first-trip test in it; and with an exit per unrolled rotation sets a and b met in such
+// copies.)  Every edge into the header has a and b in flight in this order, so the first step's
+// wait is a counted one for set a.
+// One descriptor spans both solve tables and the pad behind them (carry_rsrc); `base` is the
+// table's first step in it.
+#define MPCQP_CSTEP(X, K)                                          \
+  solve_step<PAIRED>(p.X, v);                                      \
+  __builtin_amdgcn_sched_barrier(0);                               \
+  load_solve(rs, step_off<Ops>(n, base + s + 3 + K), lane, p.X);   \
+  __builtin_amdgcn_sched_barrier(0);
+template <bool PAIRED>
+__device__ __forceinline__ void run_body_carry(Rsrc rs, int base, int n, uint32_t lane, double* v,
+                                               Pipe<SolveOps<PAIRED>>& p) {
+  typedef SolveOps<PAIRED> Ops;
+  int s = 0;
+#pragma unroll 1
+  do {
+    __builtin_amdgcn_sched_barrier(0);
+    load_solve(rs, step_off<Ops>(n, base + s + 2), lane, p.c);
+    __builtin_amdgcn_sched_barrier(0);
+    MPCQP_CSTEP(a, 0) MPCQP_CSTEP(b, 1)
+    solve_step<PAIRED>(p.c, v);
+    s += 3;
+  } while (s < n);
+}
+#undef MPCQP_CSTEP
+// the forward and backward tables with the pad behind them as one table: ImageBuilder::chain lays
+// them out back to back, [fwd][bwd][first TABLE_PAD_STEPS steps of fwd]
+__device__ __forceinline__ Rsrc carry_rsrc(const DevPlan& P) {
+  return table_rsrc(P.fwd, P.nfwd + P.nbwd, SOLVE_STEP_WORDS);
+}
+// (re)start of a carried pipeline: steps 0 and 1 into sets a and b
+template <bool PAIRED>
+__device__ __forceinline__ void carry_restart(Rsrc rs, int n, uint32_t lane, Pipe<SolveOps<PAIRED>>& p) {
+  typedef SolveOps<PAIRED> Ops;
+  __builtin_amdgcn_sched_barrier(0);
+  load_solve(rs, step_off<Ops>(n, 0), lane, p.a);
+  __builtin_amdgcn_sched_barrier(0);
+  load_solve(rs, step_off<Ops>(n, 1), lane, p.b);
+  __builtin_amdgcn_sched_barrier(0);
+}
 struct FacOps {
   typedef FacRec Rec;
   static constexpr int STRIDE = FAC_STEP_WORDS;
@@ -1563,10 +1618,12 @@ __device__ __forceinline__ void scale_finish(const KParams& p, int inst, bool re
 // KM_MATPF matrix operands one step ahead (diagnostic, rejected); KM_MVG the resident scaled values
 // in the wave's global slab (Plan::mv_global); KM_MREG matrix operands in registers (MatRegs)
 enum { KM_LDS = 0, KM_MATPF = 1, KM_MVG = 2, KM_MREG = 3 };
-template <int RN, int RM, bool PAIRED, int KM>
+template <int RN, int RM, bool PAIRED, int KM, int RP>
 __device__ __forceinline__ void solve_instance(const KParams& p, int inst, double* v, double* scr,
                                                int lane) {
   constexpr bool MATPF = KM == KM_MATPF, MVG = KM == KM_MVG, MREG = KM == KM_MREG;
+  constexpr bool CARRY = RP == RP_CARRY;
+  static_assert(!CARRY || KM == KM_LDS, "the carried record pipeline is the KM_LDS kernel's");
   const DevPlan& P = p.pl;
   const int n = P.n, m = P.m;
   const Slab sb = slab_of(P, scr);
@@ -1701,10 +1758,15 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
   Pipe<SolveOps<PAIRED>> sp;
   PipeC spc;
   const SolveOps<PAIRED> sops{v};
-  const Rsrc rs_fwd = MREG ? table_rsrc(P.fwdc, P.nfwd, SOLVEC_STEP_WORDS)
-                           : table_rsrc(P.fwd, P.nfwd, SOLVE_STEP_WORDS);
-  const Rsrc rs_bwd = MREG ? table_rsrc(P.bwdc, P.nbwd, SOLVEC_STEP_WORDS)
-                           : table_rsrc(P.bwd, P.nbwd, SOLVE_STEP_WORDS);
+  const Rsrc rs_fwd = MREG    ? table_rsrc(P.fwdc, P.nfwd, SOLVEC_STEP_WORDS)
+                      : CARRY ? carry_rsrc(P)
+                              : table_rsrc(P.fwd, P.nfwd, SOLVE_STEP_WORDS);
+  const Rsrc rs_bwd = MREG    ? table_rsrc(P.bwdc, P.nbwd, SOLVEC_STEP_WORDS)
+                      : CARRY ? rs_fwd
+                              : table_rsrc(P.bwd, P.nbwd, SOLVE_STEP_WORDS);
+  // carried pipeline: the step counts as opaque SGPR values, like the loop bounds below
+  int nfwd_s = P.nfwd, nbwd_s = P.nbwd;
+  if constexpr (CARRY) asm volatile("" : "+s"(nfwd_s), "+s"(nbwd_s));
   // the diagonal pass's 1/D in registers between factorizations ((2, 4) bucket: 12 VGPRs; six
   // LDS reads fewer per iteration)
   constexpr bool DREG = RN == 2 && !MREG;
@@ -1722,12 +1784,15 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
   int max_iter = p.s.max_iter;
   int chk_s = chk, ar_s = ar_int;
   asm volatile("" : "+s"(max_iter), "+s"(chk_s), "+s"(ar_s));
+  // a carried pipeline (RP_CARRY) enters every iteration with forward steps 0 and 1 in flight in
+  // sets a and b: from here, from the restart behind a check block, or out of the backward solve
+  if constexpr (CARRY) carry_restart(rs_fwd, P.nfwd, (uint32_t)lane, sp);
   for (iter = 1; iter <= max_iter; ++iter) {
     T_COUNT(T_ITERS);
     T_BEGIN(t_v0);
     if constexpr (MREG)  // lands while the right-hand side is formed
       prefetch_c(rs_fwd, P.nfwd, (uint32_t)lane, spc);
-    else
+    else if constexpr (!CARRY)
       prefetch(rs_fwd, P.nfwd, (uint32_t)lane, sp);
     double xp[RN], zp[RM], bz[RM];
     uint32_t wbits = wcp, bbits = bcp;  // opaque per iteration (slot_mask)
@@ -1758,13 +1823,15 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
       run_body_r<PAIRED>(rs_fwd, P.nfwd, (uint32_t)lane, v, spc, M.m[0]);
     else if constexpr (MATPF)
       run_body_pf<PAIRED>(rs_fwd, P.nfwd, (uint32_t)lane, v, sp);
+    else if constexpr (CARRY)  // leaves backward steps 0 and 1 in sets a and b
+      run_body_carry<PAIRED>(rs_fwd, 0, nfwd_s, (uint32_t)lane, v, sp);
     else
       run_body(rs_fwd, P.nfwd, (uint32_t)lane, sops, sp);
     T_END(T_FWD, t_fw);
     T_BEGIN(t_v1);
     if constexpr (MREG)  // lands during the diagonal pass
       prefetch_c(rs_bwd, P.nbwd, (uint32_t)lane, spc);
-    else
+    else if constexpr (!CARRY)
       prefetch(rs_bwd, P.nbwd, (uint32_t)lane, sp);
     {
       // C = (1/D) W; W restarts at 0, or at C where the row's identity term is folded into it
@@ -1793,6 +1860,8 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
       run_body_r<PAIRED>(rs_bwd, P.nbwd, (uint32_t)lane, v, spc, M.m[1]);
     else if constexpr (MATPF)
       run_body_pf<PAIRED>(rs_bwd, P.nbwd, (uint32_t)lane, v, sp);
+    else if constexpr (CARRY)  // leaves forward steps 0 and 1 (the pad copy) in sets a and b
+      run_body_carry<PAIRED>(rs_fwd, nfwd_s, nbwd_s, (uint32_t)lane, v, sp);
     else
       run_body(rs_bwd, P.nbwd, (uint32_t)lane, sops, sp);
     T_END(T_BWD, t_bw);
@@ -1876,6 +1945,12 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
       }
     }
     T_END(T_ADAPT, t_ad);
+    if constexpr (CARRY) {
+      // Behind a check block the pipeline restarts: sets a and b, in flight out of the backward
+      // solve, are not read again, so the check blocks hold no carried record.  Otherwise they
+      // hold forward steps 0 and 1 (the pad copy behind the backward table).
+      if (can_check || adapt) carry_restart(rs_fwd, P.nfwd, (uint32_t)lane, sp);
+    }
     T_END(T_CHECK, t_ck);
 #ifdef MPCQP_TIMING
     // the check slot split: iterations that run the residuals (check or rho adaptation) / the rest
@@ -1965,7 +2040,7 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
 #ifndef MPCQP_WAVES_PER_EU
 #define MPCQP_WAVES_PER_EU 1
 #endif
-template <int RN, int RM, bool PAIRED, int KM>
+template <int RN, int RM, bool PAIRED, int KM, int RP = RP_RESTART>
 __global__ void __launch_bounds__(64, KM == KM_MVG ? 2 : MPCQP_WAVES_PER_EU) qp_batch_kernel(KParams p) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int lane = (int)threadIdx.x;
@@ -1987,7 +2062,7 @@ __global__ void __launch_bounds__(64, KM == KM_MVG ? 2 : MPCQP_WAVES_PER_EU) qp_
     // out of the instance loop (MPCQP_OPAQUE_LANE_RN above)
     int ilane = lane;
     if constexpr (RN >= MPCQP_OPAQUE_LANE_RN) asm volatile("" : "+v"(ilane));
-    solve_instance<RN, RM, PAIRED, KM>(p, (int)inst, v, scr, ilane);
+    solve_instance<RN, RM, PAIRED, KM, RP>(p, (int)inst, v, scr, ilane);
     LDS_FENCE();
   }
 }
@@ -2047,8 +2122,10 @@ __global__ void update_P_kernel(double* setup, int setup_stride, double* W, cons
 typedef void (*kernel_fn)(KParams);
 
 // Every MPCQP_* override below is a diagnostic: honoured only with MPCQP_DIAGNOSTICS=1 (diag_env)
+// carry: the one-wave KM_LDS kernel of the (2, 4) bucket with the carried record pipeline (the
+// handle's choice, made once: record_carry below); every other kernel restarts it per solve
 template <int RN, int RM>
-kernel_fn pick(bool paired, int waves, bool matpf, bool mvg, bool mreg) {
+kernel_fn pick(bool paired, int waves, bool matpf, bool mvg, bool mreg, bool carry) {
   // two waves, the solve steps on the first; MPCQP_W0DIAG=1: the diagonal pass too (mode 3,
   // measured equal to mode 2 at N = 40)
   if (waves == 3)
@@ -2071,12 +2148,18 @@ kernel_fn pick(bool paired, int waves, bool matpf, bool mvg, bool mreg) {
   }
   if (matpf)
     return paired ? qp_batch_kernel<RN, RM, true, KM_MATPF> : qp_batch_kernel<RN, RM, false, KM_MATPF>;
+  if constexpr (RN == 2) {
+    if (carry)
+      return paired ? qp_batch_kernel<RN, RM, true, KM_LDS, RP_CARRY>
+                    : qp_batch_kernel<RN, RM, false, KM_LDS, RP_CARRY>;
+  }
   return paired ? qp_batch_kernel<RN, RM, true, KM_LDS> : qp_batch_kernel<RN, RM, false, KM_LDS>;
 }
 
 // RN = ceil(n/64) and RM = ceil(m/64) rounded up to the instantiated buckets; the plan's step kind
 // and waves per instance
-kernel_fn select_kernel(int n, int m, bool paired, int waves, bool matpf, bool mvg, bool mreg) {
+kernel_fn select_kernel(int n, int m, bool paired, int waves, bool matpf, bool mvg, bool mreg,
+                        bool carry) {
   int rn = 0, rm = 0;
   if (!kernel_bucket(n, m, rn, rm)) return nullptr;
 #ifdef MPCQP_DEV20
@@ -2087,11 +2170,14 @@ kernel_fn select_kernel(int n, int m, bool paired, int waves, bool matpf, bool m
     return paired ? qp_pair_kernel<2, 4, true, 2> : qp_pair_kernel<2, 4, false, 2>;
 #endif
   if (rn != 2 || waves != 1 || matpf || mvg || mreg) return nullptr;
+  if (carry)
+    return paired ? qp_batch_kernel<2, 4, true, KM_LDS, RP_CARRY>
+                  : qp_batch_kernel<2, 4, false, KM_LDS, RP_CARRY>;
   return paired ? qp_batch_kernel<2, 4, true, KM_LDS> : qp_batch_kernel<2, 4, false, KM_LDS>;
 #else
-  if (rn == 2) return pick<2, 4>(paired, waves, matpf, mvg, mreg);
+  if (rn == 2) return pick<2, 4>(paired, waves, matpf, mvg, mreg, carry);
 #ifndef MPCQP_ONLY_SMALL
-  if (rn == 4) return pick<4, 8>(paired, waves, matpf, mvg, mreg);
+  if (rn == 4) return pick<4, 8>(paired, waves, matpf, mvg, mreg, false);
 #endif
   return nullptr;
 #endif
@@ -2106,6 +2192,18 @@ bool use_mreg(const Plan& pl) {
   const bool fits = pl.waves == 1 && !pl.mat_first && !pl.mv_global && pl.nfwd <= MREG_STEPS &&
                     pl.nbwd <= MREG_STEPS && kernel_bucket(pl.n, pl.m, rn, rm) && rn == 2;
   return fits && diag_env_int("MPCQP_MREG", MREG_DEFAULT) != 0;
+}
+
+// The record pipeline carried across the tables (RP_CARRY): the image allows it (build_dev_image:
+// one-wave KM_LDS plan, step counts multiples of three) and the plan is of the (2, 4) bucket, the
+// only one with the kernel.  MPCQP_RECORD_PIPE=restart keeps the restart per solve on such a
+// handle (diagnostics: A/B runs, tests/test_gpu_record_pipeline.py); MPCQP_RECORD_PIPE=carry makes
+// mpcqp_create refuse a handle that would restart.
+bool record_carry(const Plan& pl, const DevImage& img) {
+  int rn = 0, rm = 0;
+  if (!img.carry || !kernel_bucket(pl.n, pl.m, rn, rm) || rn != 2) return false;
+  const char* e = diag_env("MPCQP_RECORD_PIPE");
+  return !(e && strcmp(e, "restart") == 0);
 }
 
 }  // namespace
@@ -2205,8 +2303,11 @@ int mpcqp_create(const mpcqp_structure* st, const mpcqp_settings* s, int32_t bat
   DevImage img;
   std::string err;
   if (int rc = build_dev_image(pl, mreg, img, err)) return fail(rc, err);
+  const bool carry = record_carry(pl, img);
+  if (const char* e = diag_env("MPCQP_RECORD_PIPE"); e && strcmp(e, "carry") == 0 && !carry)
+    return fail(MPCQP_E_UNSUPPORTED, "MPCQP_RECORD_PIPE=carry: this plan's record pipeline cannot be carried");
   h->kern = select_kernel(pl.n, pl.m, pl.paired, pl.waves == 2 ? (pl.split_steps ? 2 : 3) : 1,
-                          pl.mat_first, pl.mv_global, mreg);
+                          pl.mat_first, pl.mv_global, mreg, carry);
   if (!h->kern) return fail(MPCQP_E_UNSUPPORTED, "problem dimensions exceed the instantiated kernels");
   if (!dev_alloc(h, h->d_blob, img.blob.size())) return fail(MPCQP_E_HIP, "hipMalloc(structure)");
   if (hipMemcpy(h->d_blob, img.blob.data(), img.blob.size(), hipMemcpyHostToDevice) != hipSuccess)

@@ -119,10 +119,13 @@ struct ImageBuilder {
   // Two tables that run one after the other (forward then backward solve; factorization then its
   // block-inverse tail), laid out as [A][B][the first TABLE_PAD_STEPS steps of A]: the record
   // pipelines' look-ahead loads past the end of A read B's first steps -- the very lines B's own
-  // prefetch loads next, then L1 hits -- and B's read A's, which the next iteration loads (the
-  // look-ahead loads are never executed, so their content does not matter).  Measured neutral on
-  // the N = 20 bench (945k vs 944k solves/s: the shared zero pads were already L1-resident;
-  // DESIGN.md, Record traffic), kept because it takes the pads' lines out of the L1 working set.
+  // prefetch loads next, then L1 hits -- and B's read A's, which the next iteration loads.  The
+  // restarting pipelines never execute what the look-ahead loads deliver, but a carried pipeline
+  // (engine.hip RP_CARRY) does: its look-ahead sets past A are steps 0 and 1 of B's solve, and those
+  // past B steps 0 and 1 of A's next one, so the copy behind B has to be A's steps (an A shorter
+  // than the pad leaves zero steps there: build_dev_image then refuses the carry-over).  Measured
+  // neutral on the N = 20 bench as a layout alone (945k vs 944k solves/s: the shared zero pads were
+  // already L1-resident; DESIGN.md, Record traffic).
   void chain(const uint32_t*& fA, const uint32_t*& fB, const std::vector<uint32_t>& A,
              const std::vector<uint32_t>& B, int stride_words) {
     const size_t pad = (size_t)TABLE_PAD_STEPS * stride_words;
@@ -176,6 +179,11 @@ int build_dev_image(const Plan& pl, bool mreg, DevImage& img, std::string& err) 
   DevPlan& dp = img.dp;
   b.chain(dp.fac, dp.tail, pl.fac, pl.tail, FAC_STEP_WORDS);
   b.chain(dp.fwd, dp.bwd, pl.fwd, pl.bwd, SOLVE_STEP_WORDS);
+  // the carried record pipeline executes the look-ahead sets: both counts multiples of three (the
+  // rotation then leaves them in the sets the next solve reads first), and no table shorter than
+  // the pad, whose copy behind the backward table would be zero-filled
+  img.carry = pl.waves == 1 && !pl.mat_first && !pl.mv_global && !mreg && pl.nfwd % 3 == 0 &&
+              pl.nbwd % 3 == 0 && pl.nfwd >= TABLE_PAD_STEPS && pl.nbwd >= TABLE_PAD_STEPS;
   b.put(dp.Lcol, pl.Lcol);
   b.put(dp.slotP, pl.slotP), b.put(dp.slotA, pl.slotA);
   b.put(dp.slotRho, pl.slotRho), b.put(dp.slotSig, pl.slotSig);
