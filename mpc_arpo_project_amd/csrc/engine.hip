@@ -268,13 +268,17 @@ __device__ __forceinline__ void seq_sum2(const double* a, int ca, const double* 
 __device__ __forceinline__ double sum_slack(double A, int cnt) {
   return (8.0 * cnt) * (0x1p-53 * A) + 0x1p-1060 * cnt;
 }
-__device__ __forceinline__ bool seq_sum_lt(const double* buf, int cnt, double T, double A, double thr) {
+// C: the wave context (below).  T and A are all-reduced, so the instance's waves decide alike; the
+// near-tie reads every wave's staged terms, hence the sync before buf is staged in again.
+template <class Cx>
+__device__ __forceinline__ bool seq_sum_lt(const KParams& p, double* v, const Cx& C, const double* buf,
+                                           int cnt, double T, double A, double thr) {
   const double b = sum_slack(A, cnt);
   if (T + b < thr) return true;
   if (T - b >= thr) return false;
   LDS_FENCE();
   const bool lt = seq_sum(buf, cnt) < thr;
-  LDS_FENCE();
+  C.sync(p, v);
   return lt;
 }
 __device__ __forceinline__ double limit_scaling(double d) {
@@ -789,6 +793,149 @@ __device__ __forceinline__ Slab slab_of(const DevPlan& P, double* scr) {
   s.MV = scr + ((P.n + P.m + 1) & ~1);  // 16-byte aligned (the slab base is)
   return s;
 }
+// ---- wave contexts.  The check path (residual mat-vecs and norms, residuals, termination,
+// certificates, rho estimate, bounds, solution store) is written once, over the context C of the
+// wave that runs it: One for the one-wave kernel, Wv for each wave of the two-wave kernel
+// (engine_pair.inc).  A context gives
+//   lane, xo, zo   the wave's lane and its first n- / m-vector slot: slot r holds element
+//                  lane + 64 (r + xo) (resp. zo); WAVES / THREADS per instance, tid(), first()
+//   all<K>()       all-reduce of K wave-uniform values over the instance's waves
+//   sync()         this phase's LDS traffic ordered before the next phase's, in every wave
+//   stage()        the wave's staging slots of the long outputs' products (accumulator region C,
+//                  free during the checks); mv(): the base of the resident scaled values
+// With One the offsets are compile-time zeros, owns() is true and all() is the identity: the
+// shared code folds to the one-wave kernel's own operations.  Where the two kernels' forms differ
+// in structure, each keeps its own behind an `if constexpr` on Cx::WAVES (Two waves per
+// instance).
+
+// LDS barrier of the two waves: this wave's LDS operations complete, then both meet
+#define BAR2()                                                                              \
+  do {                                                                                      \
+    LDS_FENCE();                                                                            \
+    __builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0); vmcnt and expcnt left at their max */ \
+    __builtin_amdgcn_s_barrier();                                                           \
+    LDS_FENCE();                                                                            \
+  } while (0)
+
+// BAR2_X(v, xid): the barrier of the diagnostic -DMPCQP_PAIR_CHECKS build -- an LDS-counter
+// barrier with a bounded wait instead of s_barrier, so a divergence of the two waves' barrier
+// sequences is reported (the hand-off check in qp_pair_kernel sees the poison flag and sets the
+// instance's status to -1000) instead of hanging the GPU; the product build's
+// BAR2.  Counters over the hand-off slot XID (4 doubles in checks builds): ints [4], [5] the
+// barriers waves 0 / 1 have reached, [6] the poison flag.
+#ifdef MPCQP_PAIR_CHECKS
+constexpr int PAIR_BAR_POLLS = 1 << 16;  // x s_sleep 4 (~256 cycles): ~17M cycles, far above any legit wait
+__device__ __noinline__ void bar2_checked(double* v, int xid) {
+  volatile int* ck = reinterpret_cast<volatile int*>(v + xid) + 4;
+  const int w = (int)(threadIdx.x >> 6);
+  LDS_FENCE();
+  __builtin_amdgcn_s_waitcnt(0xC07F);  // this wave's LDS operations complete
+  int mine = 0;
+  if ((threadIdx.x & 63) == 0) mine = ck[w] = ck[w] + 1;
+  mine = __builtin_amdgcn_readfirstlane(__shfl(mine, 0, 64));
+  for (int t = 0;; ++t) {
+    if (ck[2] != 0 || ck[1 - w] >= mine) break;
+    if (t >= PAIR_BAR_POLLS) {
+      if ((threadIdx.x & 63) == 0) ck[2] = 1;
+      break;
+    }
+    __builtin_amdgcn_s_sleep(4);
+  }
+  LDS_FENCE();
+}
+#define BAR2_X(v, xid) bar2_checked((v), (xid))
+// the test of the checked barrier itself (tests/test_gpu_pair_checks.py): when set (host:
+// mpcqp_debug_pair_inject), wave 1 of workgroup 0 skips one barrier -- the right-hand side's of the
+// first ADMM iteration of its first instance -- and the divergence must come back as status -1000
+__device__ int g_pair_inject = 0;
+#else
+#define BAR2_X(v, xid) BAR2()
+#endif
+
+// The one wave of the one-wave kernel.  mvb: the LDS image, or the wave's slab under KM_MVG
+struct One {
+  static constexpr int WAVES = 1, THREADS = 64;
+  static constexpr int xo = 0, zo = 0;
+  int lane;
+  const double* mvb;
+  template <int K>
+  __device__ __forceinline__ void all(const KParams&, double*, const double (&mine)[K],
+                                      const bool (&)[K], double (&out)[K]) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) out[k] = mine[k];
+  }
+  __device__ __forceinline__ void sync(const KParams&, double*) const { LDS_FENCE(); }
+  __device__ __forceinline__ double* stage(const DevPlan& P, double* v) const { return v + P.CACC; }
+  __device__ __forceinline__ const double* mv(const double*) const { return mvb; }
+  __device__ __forceinline__ int tid() const { return lane; }
+  __device__ __forceinline__ bool first() const { return lane == 0; }
+};
+
+// Where a wave of the two-wave kernel sits: w (0 / 1), lane, its first n-slot xo and m-slot zo,
+// the exchange buffer phase (two buffers alternate, so a wave can write the next exchange while the
+// other still reads the last one: it cannot pass the barrier after that before the other wave has
+// read)
+struct Wv {
+  static constexpr int WAVES = 2, THREADS = 128;
+  int w, lane, xo, zo;
+  int ph;
+#ifdef MPCQP_PAIR_CHECKS
+  int nx;   // exchanges this wave made (diagnostic builds: both waves must agree at every hand-off)
+  int inj;  // this wave skips one barrier (g_pair_inject)
+#endif
+  // out[k] = op_k(wave 0's, wave 1's) through the exchange slots: both waves read the same two
+  // values, so every decision taken on them is identical in both
+  template <int K>
+  __device__ __forceinline__ void all(const KParams& p, double* v, const double (&mine)[K],
+                                      const bool (&is_sum)[K], double (&out)[K]) {
+    static_assert(K <= XCH_K, "exchange buffer");
+    double* buf = v + p.pl.XCH + ph * (2 * XCH_K);
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) buf[w * XCH_K + k] = mine[k];
+    }
+    BAR2_X(v, p.pl.XID);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const double a = buf[k], b = buf[XCH_K + k];
+      out[k] = is_sum[k] ? a + b : dmaxd(a, b);
+    }
+    ph ^= 1;
+#ifdef MPCQP_PAIR_CHECKS
+    nx++;
+#endif
+  }
+  __device__ __forceinline__ void sync(const KParams& p, double* v) const { BAR2_X(v, p.pl.XID); }
+  // the wave's half of the accumulator region C
+  __device__ __forceinline__ double* stage(const DevPlan& P, double* v) const {
+    return v + P.CACC + w * (32 * P.NKS);
+  }
+  __device__ __forceinline__ const double* mv(const double* v) const { return v; }
+  __device__ __forceinline__ int tid() const { return lane + 64 * w; }
+  __device__ __forceinline__ bool first() const { return w == 0 && lane == 0; }
+};
+template <class Cx>
+__device__ __forceinline__ double xch_max(const KParams& p, double* v, Cx& C, double x) {
+  const double m[1] = {x};
+  const bool s[1] = {false};
+  double o[1];
+  C.template all<1>(p, v, m, s, o);
+  return o[0];
+}
+template <class Cx>
+__device__ __forceinline__ double xch_sum(const KParams& p, double* v, Cx& C, double x) {
+  const double m[1] = {x};
+  const bool s[1] = {true};
+  double o[1];
+  C.template all<1>(p, v, m, s, o);
+  return o[0];
+}
+// element o is one of the wave's slots [off, off + R) (wave-uniform)
+template <class Cx>
+__device__ __forceinline__ bool owns(const Cx&, int o, int off, int R) {
+  return Cx::WAVES == 1 || (o >= 64 * off && o < 64 * (off + R));
+}
+
 // residual mat-vec out[r] = sum_k v[vpos[t]] * in[in_idx[t]], t = off_r + 64 k + lane, for every
 // slot r of the instance (terms in order): the scaled values are the LDS-resident copy (MV), the
 // two index lists are shared by all instances.  All index loads are issued before the first use.
@@ -801,13 +948,17 @@ struct EllTk {
   uint32_t tk[R][KMAX];
   uint32_t lp[ELL_LPF], li[ELL_LPF];
 };
-template <int R, int KMAX>
-__device__ __forceinline__ void ell_load(const EllDev& e, EllTk<R, KMAX>& t, int lane) {
+// (every mat-vec and norm below: rows [off, off + R) of the ELL for the wave context C, long
+// outputs by the wave that owns them)
+template <class Cx, int R, int KMAX>
+__device__ __forceinline__ void ell_load(const EllDev& e, EllTk<R, KMAX>& t, const Cx& C, int off) {
   static_assert(KMAX % 4 == 0, "lane-major term rows are loaded 16 bytes at a time");
+  const int lane = C.lane;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    if (e.K[r] == 0) continue;  // slot beyond the instance (wave-uniform)
-    const uint4* row = reinterpret_cast<const uint4*>(e.pk + (size_t)(r * 64 + lane) * KMAX);
+    const int rg = r + off;
+    if (e.K[rg] == 0) continue;  // slot beyond the instance (wave-uniform)
+    const uint4* row = reinterpret_cast<const uint4*>(e.pk + (size_t)(rg * 64 + lane) * KMAX);
 #pragma unroll
     for (int q = 0; q < KMAX / 4; ++q) {
       const uint4 w = row[q];
@@ -817,7 +968,7 @@ __device__ __forceinline__ void ell_load(const EllDev& e, EllTk<R, KMAX>& t, int
 #pragma unroll
   for (int L = 0; L < ELL_LPF; ++L) {
     t.lp[L] = 0, t.li[L] = 0;
-    if (L < e.nlong && lane < e.long_cnt[L]) {
+    if (L < e.nlong && owns(C, e.long_out[L], off, R) && lane < e.long_cnt[L]) {
       const int q = e.long_off[L] + lane;
       t.lp[L] = e.vpos[q], t.li[L] = e.in[q];
     }
@@ -829,16 +980,18 @@ __device__ __forceinline__ void ell_load(const EllDev& e, EllTk<R, KMAX>& t, int
 // the symmetric P x), each product rounded before it is added (no contraction, above).  Long
 // outputs: the products of all lanes staged in LDS (stg, wave-private, long_cnt doubles) and summed
 // in term order by seq_sum.
-template <int R, int KMAX>
+template <class Cx, int R, int KMAX>
 __device__ __forceinline__ void ell_apply(const EllDev& e, const EllTk<R, KMAX>& t, const double* mv,
-                                          const double* in, double (&out)[R], int lane, double* stg) {
+                                          const double* in, double (&out)[R], const Cx& C, int off,
+                                          double* stg) {
   constexpr int LPF = ELL_LPF;
   const uint32_t(&lp)[LPF] = t.lp;
   const uint32_t(&li)[LPF] = t.li;
+  const int lane = C.lane;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     double s = 0.0;
-    if (e.K[r] != 0) {
+    if (e.K[r + off] != 0) {
       double a[KMAX], b[KMAX];
 #pragma unroll
       for (int k = 0; k < KMAX; ++k) a[k] = mv[t.tk[r][k] & 0xffffu], b[k] = in[t.tk[r][k] >> 16];
@@ -847,11 +1000,13 @@ __device__ __forceinline__ void ell_apply(const EllDev& e, const EllTk<R, KMAX>&
     }
     out[r] = s;
   }
-  if (e.nlong == 0) return;
+  if constexpr (Cx::WAVES == 1)
+    if (e.nlong == 0) return;
   // every long output's products staged first (each output at its own offset: mpcqp_create checks
   // that they fit), then the sequential sums two at a time
   int base = 0;
   for (int L = 0; L < e.nlong; ++L) {
+    if (!owns(C, e.long_out[L], off, R)) continue;  // wave-uniform
     int t0 = lane;
 #pragma unroll
     for (int k = 0; k < LPF; ++k)
@@ -865,31 +1020,56 @@ __device__ __forceinline__ void ell_apply(const EllDev& e, const EllTk<R, KMAX>&
     }
     base += e.long_cnt[L];
   }
+  if constexpr (Cx::WAVES > 1)
+    if (base == 0) return;  // none of them is this wave's
   LDS_FENCE();
   base = 0;
-  for (int L = 0; L < e.nlong; L += 2) {
-    const int c0 = e.long_cnt[L], c1 = L + 1 < e.nlong ? e.long_cnt[L + 1] : 0;
-    double s0, s1 = 0.0;
-    if (c1)
-      seq_sum2(stg + base, c0, stg + base + c0, c1, s0, s1);
-    else
-      s0 = seq_sum(stg + base, c0);
-    const int o0 = e.long_out[L], o1 = c1 ? e.long_out[L + 1] : -1;
+  if constexpr (Cx::WAVES == 1) {  // every output is the wave's: neighbours pair up
+    for (int L = 0; L < e.nlong; L += 2) {
+      const int c0 = e.long_cnt[L], c1 = L + 1 < e.nlong ? e.long_cnt[L + 1] : 0;
+      double s0, s1 = 0.0;
+      if (c1)
+        seq_sum2(stg + base, c0, stg + base + c0, c1, s0, s1);
+      else
+        s0 = seq_sum(stg + base, c0);
+      const int o0 = e.long_out[L], o1 = c1 ? e.long_out[L + 1] : -1;
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (o0 == lane + 64 * r) out[r] = s0;
-      if (o1 == lane + 64 * r) out[r] = s1;
+      for (int r = 0; r < R; ++r) {
+        if (o0 == lane + 64 * r) out[r] = s0;
+        if (o1 == lane + 64 * r) out[r] = s1;
+      }
+      base += c0 + c1;
     }
-    base += c0 + c1;
+  } else {  // the wave's outputs pair up among themselves
+    auto put = [&](int o, double x) {
+#pragma unroll
+      for (int r = 0; r < R; ++r)
+        if (o == lane + 64 * (r + off)) out[r] = x;
+    };
+    int po = -1, pc = 0, pb = 0;  // an owned output waiting for its partner chain
+    for (int L = 0; L < e.nlong; ++L) {
+      const int o = e.long_out[L], c = e.long_cnt[L];
+      if (!owns(C, o, off, R)) continue;
+      if (po < 0) {
+        po = o, pc = c, pb = base;
+      } else {
+        double s0, s1;
+        seq_sum2(stg + pb, pc, stg + base, c, s0, s1);
+        put(po, s0), put(o, s1);
+        po = -1;
+      }
+      base += c;
+    }
+    if (po >= 0) put(po, seq_sum(stg + pb, pc));
   }
   LDS_FENCE();
 }
-template <int R, int KMAX>
+template <int R, int KMAX, class Cx>
 __device__ __forceinline__ void ell_mv(const EllDev& e, const double* mv, const double* in,
-                                       double (&out)[R], int lane, double* stg) {
+                                       double (&out)[R], const Cx& C, int off, double* stg) {
   EllTk<R, KMAX> t;
-  ell_load(e, t, lane);
-  ell_apply(e, t, mv, in, out, lane, stg);
+  ell_load(e, t, C, off);
+  ell_apply(e, t, mv, in, out, C, off, stg);
 }
 // The Ruiz passes' index lists, loaded once per solve into registers (lane-major, 8 bytes = four
 // u16 slots per load; shared by every instance: L1/L2 hits): the passes then read only values.
@@ -898,12 +1078,13 @@ struct EllIdx {
   uint32_t w[R][KMAX / 2];  // two u16 overlay slots per register
 };
 template <int R, int KMAX>
-__device__ __forceinline__ void load_idx(const EllDev& e, EllIdx<R, KMAX>& ix, int lane) {
+__device__ __forceinline__ void load_idx(const EllDev& e, EllIdx<R, KMAX>& ix, int lane, int off) {
   static_assert(KMAX % 4 == 0, "index rows are loaded 8 bytes at a time");
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    if (e.K[r] == 0) continue;
-    const uint2* row = reinterpret_cast<const uint2*>(e.sk + (size_t)(r * 64 + lane) * KMAX);
+    const int rg = r + off;
+    if (e.K[rg] == 0) continue;
+    const uint2* row = reinterpret_cast<const uint2*>(e.sk + (size_t)(rg * 64 + lane) * KMAX);
 #pragma unroll
     for (int q = 0; q < KMAX / 4; ++q) {
       const uint2 w = row[q];
@@ -938,15 +1119,17 @@ __device__ __forceinline__ uint32_t ell_kflags(const EllDev& e) {
   return f;
 }
 // KF = false ((4, 8) bucket): the flags are not used (there they moved a kernel-argument reload
-// into the ADMM loop head, tests/test_isa_hot_loops.py)
-template <bool KF, int R, int KMAX>
+// into the ADMM loop head, tests/test_isa_hot_loops.py), nor by the two-wave kernel
+template <bool KF, class Cx, int R, int KMAX>
 __device__ __forceinline__ void ell_absmax_r(const EllDev& e, const EllIdx<R, KMAX>& ix, uint32_t kf,
-                                             const double* v, double (&out)[R], int lane) {
+                                             const double* v, double (&out)[R], const Cx& C, int off) {
+  static_assert(!KF || Cx::WAVES == 1, "the flags are those of slots [0, R)");
+  const int lane = C.lane;
   const uint32_t kfu = KF ? __builtin_amdgcn_readfirstlane(kf) : 0u;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     double mx = 0.0;
-    if (KF ? (kfu & (1u << r)) != 0 : e.K[r] != 0) {
+    if (KF ? (kfu & (1u << r)) != 0 : e.K[r + off] != 0) {
       double b[KMAX];
 #pragma unroll
       for (int k = 0; k < KMAX; ++k) {
@@ -959,13 +1142,14 @@ __device__ __forceinline__ void ell_absmax_r(const EllDev& e, const EllIdx<R, KM
     out[r] = mx;
   }
   for (int L = 0; L < e.nlong; ++L) {
+    if (!owns(C, e.long_out[L], off, R)) continue;
     double mx = 0.0;
     for (int t = lane; t < e.long_cnt[L]; t += 64) mx = dmaxd(fabs(v[e.src[e.long_off[L] + t]]), mx);
     mx = wave_max(mx);
     const int o = e.long_out[L];
 #pragma unroll
     for (int r = 0; r < R; ++r)
-      if (o == lane + 64 * r) out[r] = mx;
+      if (o == lane + 64 * (r + off)) out[r] = mx;
   }
 }
 // Ruiz rescale of the value overlay [P | A] (cnt = nnzP + nnzA values from S_P):
@@ -1113,24 +1297,33 @@ __device__ __forceinline__ void assemble_and_factor(const KParams& p, const Slab
 #define TACC_PARAM
 #define TACC_ARG
 #endif
-template <int RN, int RM>
+// x staged at xb for a mat-vec.  One wave stores every slot: those past n land in y's range or the
+// W padding and are overwritten or never read (a wave's LDS stores complete in order).  Of two
+// waves each stores only its elements below n: what follows them is the other wave's
+template <class Cx, int RN>
+__device__ __forceinline__ void stage_x(const Cx& C, int n, double* xb, const double (&x)[RN]) {
+#pragma unroll
+  for (int r = 0; r < RN; ++r) {
+    const int j = C.lane + 64 * (r + C.xo);
+    if (Cx::WAVES == 1 || j < n) xb[j] = x[r];
+  }
+}
+template <class Cx, int RN, int RM>
 __device__ __forceinline__ void compute_residuals(const KParams& p, Inst<RN, RM>& S, Resid<RN, RM>& R,
-                                  const Slab& sb, double* v, const double* mv, int lane TACC_PARAM) {
+                                                  double* v, Cx& C TACC_PARAM) {
   const DevPlan& P = p.pl;
-  const int n = P.n, m = P.m;
+  const int n = P.n, m = P.m, lane = C.lane;
   double* xb = v + P.W;
   double* yb = v + P.W + n;
   T_BEGIN(t_r0);
   LDS_FENCE();
-  // unconditional stores: x's slots past n land in y's range and are overwritten by the y stores
-  // that follow (a wave's LDS stores complete in order); y's slots past m stay inside the padded
-  // W region (n + 64 RM <= 64 (RN + RM) = NKP)
+  stage_x(C, n, xb, S.x);
+  // one wave: x's slots past n before the y stores that overwrite them; two waves store disjoint
+  // slots, in any order
+  if constexpr (Cx::WAVES == 1) LDS_FENCE();
 #pragma unroll
-  for (int r = 0; r < RN; ++r) xb[lane + 64 * r] = S.x[r];
-  LDS_FENCE();
-#pragma unroll
-  for (int r = 0; r < RM; ++r) yb[lane + 64 * r] = S.y[r];
-  LDS_FENCE();
+  for (int r = 0; r < RM; ++r) yb[lane + 64 * (r + C.zo)] = S.y[r];  // past m: W padding (n + 64 RM <= NKP)
+  C.sync(p, v);
   double pr = 0.0, dr = 0.0;
   T_END(T_RS0, t_r0);
   T_BEGIN(t_r1);
@@ -1139,95 +1332,122 @@ __device__ __forceinline__ void compute_residuals(const KParams& p, Inst<RN, RM>
     EllTk<RM, ELL_KA> tA;
     EllTk<RN, ELL_KP> tP;
     EllTk<RN, ELL_KAT> tT;
-    ell_load(P.eA, tA, lane);
-    ell_load(P.eP, tP, lane);
-    ell_load(P.eAt, tT, lane);
-    ell_apply(P.eA, tA, mv, xb, R.Ax, lane, v + P.CACC);  // padding terms are 0 * x
-    ell_apply(P.eP, tP, mv, xb, R.Px, lane, v + P.CACC);
-    ell_apply(P.eAt, tT, mv, yb, R.Aty, lane, v + P.CACC);
+    const double* mv = C.mv(v);
+    ell_load(P.eA, tA, C, C.zo);
+    ell_load(P.eP, tP, C, C.xo);
+    ell_load(P.eAt, tT, C, C.xo);
+    ell_apply(P.eA, tA, mv, xb, R.Ax, C, C.zo, C.stage(P, v));  // padding terms are 0 * x
+    ell_apply(P.eP, tP, mv, xb, R.Px, C, C.xo, C.stage(P, v));
+    ell_apply(P.eAt, tT, mv, yb, R.Aty, C, C.xo, C.stage(P, v));
   }
   TSYNC(R.Aty[0]);
   T_END(T_RS1, t_r1);  // the three mat-vecs together (slot rs_matvecs)
   T_BEGIN(t_r4);
 #pragma unroll
   for (int r = 0; r < RM; ++r) {
-    const int i = lane + 64 * r;
+    const int i = lane + 64 * (r + C.zo);
     if (i < m) pr = dmaxd(pr, fabs(S.Einv[r] * (R.Ax[r] - S.z[r])));
     if (i >= m) R.Ax[r] = 0.0;
   }
 #pragma unroll
   for (int r = 0; r < RN; ++r) {
-    const int j = lane + 64 * r;
+    const int j = lane + 64 * (r + C.xo);
     if (j < n) dr = dmaxd(dr, fabs(S.Dinv[r] * ((S.q[r] + R.Px[r]) + R.Aty[r])));
     if (j >= n) R.Px[r] = 0.0, R.Aty[r] = 0.0;
   }
-  S.pri_res = wave_max(pr);
-  S.dua_res = S.cinv * wave_max(dr);
+  const double mine[2] = {wave_max(pr), wave_max(dr)};
+  const bool ks[2] = {false, false};
+  double both[2];
+  C.template all<2>(p, v, mine, ks, both);  // two waves: also every read of xb / yb before W is rewritten
+  S.pri_res = both[0];
+  S.dua_res = S.cinv * both[1];
   TSYNC(S.dua_res);
   T_END(T_RS4, t_r4);
 }
 
-template <int RN, int RM>
+// The certificates' early returns depend only on all-reduced values, so the waves of an instance
+// take them together and every sync() is reached by all of them (tests/test_gpu_pair_checks.py).
+template <class Cx, int RN, int RM>
 __device__ __forceinline__ bool is_primal_infeasible(const KParams& p, Inst<RN, RM>& S, double (&dy)[RM],
-                                     const Slab& sb, const double (&Ev)[RM], double* v,
-                                     const double* mv, int lane, double eps) {
+                                                     const double (&Ev)[RM], double* v, Cx& C,
+                                                     double eps) {
   const DevPlan& P = p.pl;
+  const int lane = C.lane;
   const double thr = OSQP_INFTY * MIN_SCALING;
-  double nrm = 0.0;
+  // dy clipped to the bounds' cone and its norm; lhs = u' max(dy, 0) + l' min(dy, 0) < eps |dy|,
+  // decided on OSQP's sequential sum (the terms staged in index order in C, free during the
+  // checks; seq_sum_lt)
+  double nrm = 0.0, part = 0.0, apart = 0.0;
+  double* stg = v + P.CACC;
+  // one wave: a tiny norm returns before the terms are formed (FUSED = false: two passes); two
+  // waves: one pass and one exchange for the norm and both sums (an exchange is a barrier)
+  constexpr bool FUSED = Cx::WAVES > 1;
 #pragma unroll
   for (int r = 0; r < RM; ++r) {
-    const int i = lane + 64 * r;
+    const int i = lane + 64 * (r + C.zo);
     if (i < P.m) {
       if (S.u[r] > thr)
         dy[r] = (S.l[r] < -thr) ? 0.0 : dmind(dy[r], 0.0);
       else if (S.l[r] < -thr)
         dy[r] = dmaxd(dy[r], 0.0);
       nrm = dmaxd(nrm, fabs(Ev[r] * dy[r]));
+      if constexpr (FUSED) {
+        const double t = S.u[r] * dmaxd(dy[r], 0.0) + S.l[r] * dmind(dy[r], 0.0);
+        stg[i] = t;
+        part = part + t, apart = apart + fabs(t);
+      }
     }
   }
-  nrm = wave_max(nrm);
-  if (!(nrm > DIVISION_TOL)) return false;
-  // lhs = u' max(dy, 0) + l' min(dy, 0) < eps |dy|, decided on OSQP's sequential sum (the terms
-  // staged in C, free during the checks; seq_sum_lt)
-  double* stg = v + P.CACC;
-  double part = 0.0, apart = 0.0;
+  if constexpr (!FUSED) {
+    nrm = wave_max(nrm);
+    if (!(nrm > DIVISION_TOL)) return false;
 #pragma unroll
-  for (int r = 0; r < RM; ++r) {
-    const int i = lane + 64 * r;
-    if (i < P.m) {
-      const double t = S.u[r] * dmaxd(dy[r], 0.0) + S.l[r] * dmind(dy[r], 0.0);
-      stg[i] = t;
-      part = part + t, apart = apart + fabs(t);
+    for (int r = 0; r < RM; ++r) {
+      const int i = lane + 64 * r;
+      if (i < P.m) {
+        const double t = S.u[r] * dmaxd(dy[r], 0.0) + S.l[r] * dmind(dy[r], 0.0);
+        stg[i] = t;
+        part = part + t, apart = apart + fabs(t);
+      }
     }
+    part = wave_sum(part), apart = wave_sum(apart);
+  } else {
+    const double mine[3] = {wave_max(nrm), wave_sum(part), wave_sum(apart)};
+    const bool ks[3] = {false, true, true};
+    double b3[3];
+    C.template all<3>(p, v, mine, ks, b3);  // its barrier publishes both waves' staged terms
+    nrm = b3[0], part = b3[1], apart = b3[2];
+    if (!(nrm > DIVISION_TOL)) return false;
   }
-  if (!seq_sum_lt(stg, P.m, wave_sum(part), wave_sum(apart), eps * nrm)) return false;
+  if (!seq_sum_lt(p, v, C, stg, P.m, part, apart, eps * nrm)) return false;
   double* yb = v + P.W + P.n;
   LDS_FENCE();
 #pragma unroll
-  for (int r = 0; r < RM; ++r) yb[lane + 64 * r] = dy[r];  // slots past m: W padding
-  LDS_FENCE();
+  for (int r = 0; r < RM; ++r) yb[lane + 64 * (r + C.zo)] = dy[r];  // slots past m: W padding
+  C.sync(p, v);
   // A' dy by the residual ELL (same term order as the CSC column traversal, loads batched)
   double aty[RN];
-  ell_mv<RN, ELL_KAT>(P.eAt, mv, yb, aty, lane, v + P.CACC);
+  ell_mv<RN, ELL_KAT>(P.eAt, C.mv(v), yb, aty, C, C.xo, C.stage(P, v));
   double mx = 0.0;
 #pragma unroll
   for (int r = 0; r < RN; ++r)
-    if (lane + 64 * r < P.n) mx = dmaxd(mx, fabs(aty[r] * S.Dinv[r]));
-  mx = wave_max(mx);
+    if (lane + 64 * (r + C.xo) < P.n) mx = dmaxd(mx, fabs(aty[r] * S.Dinv[r]));
+  mx = xch_max(p, v, C, wave_max(mx));
   return mx < eps * nrm;
 }
 
-template <int RN, int RM>
+template <class Cx, int RN, int RM>
 __device__ __forceinline__ bool is_dual_infeasible(const KParams& p, Inst<RN, RM>& S, const double (&dx)[RN],
-                                   const Slab& sb, const double (&Dv)[RN], double* v,
-                                   const double* mv, int lane, double eps) {
+                                                   const double (&Dv)[RN], double* v, Cx& C,
+                                                   double eps) {
   const DevPlan& P = p.pl;
+  const int lane = C.lane;
   const double thr = OSQP_INFTY * MIN_SCALING;
   double nrm = 0.0, part = 0.0, apart = 0.0;
   double* stg = v + P.CACC;  // q' dx (vec_prod) decided on OSQP's order, the products staged in C
 #pragma unroll
   for (int r = 0; r < RN; ++r) {
-    const int j = lane + 64 * r;
+    const int j = lane + 64 * (r + C.xo);
     if (j < P.n) {
       nrm = dmaxd(nrm, fabs(Dv[r] * dx[r]));
       const double t = S.q[r] * dx[r];
@@ -1235,52 +1455,62 @@ __device__ __forceinline__ bool is_dual_infeasible(const KParams& p, Inst<RN, RM
       part = part + t, apart = apart + fabs(t);
     }
   }
-  nrm = wave_max(nrm);
-  if (!(nrm > DIVISION_TOL)) return false;
-  if (!seq_sum_lt(stg, P.n, wave_sum(part), wave_sum(apart), S.c * eps * nrm)) return false;
+  if constexpr (Cx::WAVES == 1) {  // one wave: a tiny norm returns before the sums are reduced
+    nrm = wave_max(nrm);
+    if (!(nrm > DIVISION_TOL)) return false;
+    part = wave_sum(part), apart = wave_sum(apart);
+  } else {  // two waves: one exchange for all three
+    const double mine[3] = {wave_max(nrm), wave_sum(part), wave_sum(apart)};
+    const bool ks[3] = {false, true, true};
+    double b3[3];
+    C.template all<3>(p, v, mine, ks, b3);
+    nrm = b3[0], part = b3[1], apart = b3[2];
+    if (!(nrm > DIVISION_TOL)) return false;
+  }
+  if (!seq_sum_lt(p, v, C, stg, P.n, part, apart, S.c * eps * nrm)) return false;
   double* xb = v + P.W;
   LDS_FENCE();
-#pragma unroll
-  for (int r = 0; r < RN; ++r) xb[lane + 64 * r] = dx[r];  // slots past n: inside the W region
-  LDS_FENCE();
+  stage_x(C, P.n, xb, dx);
+  C.sync(p, v);
   // P dx and A dx by the residual ELLs (same term orders as the symmetric / CSR traversals)
   double pdx[RN];
-  ell_mv<RN, ELL_KP>(P.eP, mv, xb, pdx, lane, v + P.CACC);
+  ell_mv<RN, ELL_KP>(P.eP, C.mv(v), xb, pdx, C, C.xo, C.stage(P, v));
   double mx = 0.0;
 #pragma unroll
   for (int r = 0; r < RN; ++r)
-    if (lane + 64 * r < P.n) mx = dmaxd(mx, fabs(pdx[r] * S.Dinv[r]));
-  mx = wave_max(mx);
+    if (lane + 64 * (r + C.xo) < P.n) mx = dmaxd(mx, fabs(pdx[r] * S.Dinv[r]));
+  mx = xch_max(p, v, C, wave_max(mx));
   if (!(mx < S.c * eps * nrm)) return false;
   double adx[RM];
-  ell_mv<RM, ELL_KA>(P.eA, mv, xb, adx, lane, v + P.CACC);
+  ell_mv<RM, ELL_KA>(P.eA, C.mv(v), xb, adx, C, C.zo, C.stage(P, v));
   int bad = 0;
 #pragma unroll
   for (int r = 0; r < RM; ++r) {
-    if (lane + 64 * r < P.m) {
+    if (lane + 64 * (r + C.zo) < P.m) {
       const double s = adx[r] * S.Einv[r];
       if ((S.u[r] < thr && s > eps * nrm) || (S.l[r] > -thr && s < -eps * nrm)) bad = 1;
     }
   }
-  return !__any(bad);
+  return !(xch_max(p, v, C, __any(bad) ? 1.0 : 0.0) > 0.0);
 }
 
-template <int RN, int RM>
+template <class Cx, int RN, int RM>
 __device__ __forceinline__ int check_termination(const KParams& p, Inst<RN, RM>& S, const Resid<RN, RM>& R,
-                                 double (&dy)[RM], const double (&dx)[RN], const Slab& sb,
-                                 double* v, const double* mv, int lane, bool approximate TACC_PARAM) {
+                                                 double (&dy)[RM], const double (&dx)[RN], const Slab& sb,
+                                                 double* v, Cx& C, bool approximate TACC_PARAM) {
   T_BEGIN(t_m0);
   const DevPlan& P = p.pl;
+  const int lane = C.lane;
   // the scalings D, E of the infeasibility certificates: loaded first, in flight under the norms
   double Ev[RM], Dv[RN];
 #pragma unroll
   for (int r = 0; r < RM; ++r) {
-    const int i = lane + 64 * r;
+    const int i = lane + 64 * (r + C.zo);
     Ev[r] = i < P.m ? sb.E[i] : 0.0;
   }
 #pragma unroll
   for (int r = 0; r < RN; ++r) {
-    const int j = lane + 64 * r;
+    const int j = lane + 64 * (r + C.xo);
     Dv[r] = j < P.n ? sb.D[j] : 0.0;
   }
   double eps_abs = p.s.eps_abs, eps_rel = p.s.eps_rel;
@@ -1290,7 +1520,7 @@ __device__ __forceinline__ int check_termination(const KParams& p, Inst<RN, RM>&
   double zn = 0.0, axn = 0.0, qn = 0.0, atn = 0.0, pxn = 0.0;
 #pragma unroll
   for (int r = 0; r < RM; ++r) {
-    const int i = lane + 64 * r;
+    const int i = lane + 64 * (r + C.zo);
     if (i < P.m) {
       const double ei = S.Einv[r];
       zn = dmaxd(zn, fabs(ei * S.z[r]));
@@ -1299,7 +1529,7 @@ __device__ __forceinline__ int check_termination(const KParams& p, Inst<RN, RM>&
   }
 #pragma unroll
   for (int r = 0; r < RN; ++r) {
-    const int j = lane + 64 * r;
+    const int j = lane + 64 * (r + C.xo);
     if (j < P.n) {
       const double di = S.Dinv[r];
       qn = dmaxd(qn, fabs(di * S.q[r]));
@@ -1307,8 +1537,11 @@ __device__ __forceinline__ int check_termination(const KParams& p, Inst<RN, RM>&
       pxn = dmaxd(pxn, fabs(di * R.Px[r]));
     }
   }
-  zn = wave_max(zn), axn = wave_max(axn), qn = wave_max(qn), atn = wave_max(atn);
-  pxn = wave_max(pxn);
+  const double mine[5] = {wave_max(zn), wave_max(axn), wave_max(qn), wave_max(atn), wave_max(pxn)};
+  const bool ks[5] = {false, false, false, false, false};
+  double both[5];
+  C.template all<5>(p, v, mine, ks, both);
+  zn = both[0], axn = both[1], qn = both[2], atn = both[3], pxn = both[4];
   const double eps_prim = eps_abs + eps_rel * dmaxd(zn, axn);
   const double eps_dual = eps_abs + eps_rel * (dmaxd(dmaxd(qn, atn), pxn) * S.cinv);
   bool prim_ok = false, dual_ok = false, prim_inf = false, dual_inf = false;
@@ -1318,14 +1551,17 @@ __device__ __forceinline__ int check_termination(const KParams& p, Inst<RN, RM>&
   if (S.pri_res < eps_prim)
     prim_ok = true;
   else
-    prim_inf = is_primal_infeasible(p, S, dy, sb, Ev, v, mv, lane, eps_pinf);
+    prim_inf = is_primal_infeasible(p, S, dy, Ev, v, C, eps_pinf);
   T_END(T_TM1, t_m1);
   T_BEGIN(t_m2);
   if (S.dua_res < eps_dual)
     dual_ok = true;
   else
-    dual_inf = is_dual_infeasible(p, S, dx, sb, Dv, v, mv, lane, eps_dinf);
+    dual_inf = is_dual_infeasible(p, S, dx, Dv, v, C, eps_dinf);
   T_END(T_TM2, t_m2);
+  // two waves: the certificates' staging in W read by both before either rewrites W (one wave's
+  // LDS operations are ordered as issued)
+  if constexpr (Cx::WAVES > 1) C.sync(p, v);
   if (prim_ok && dual_ok) return approximate ? MPCQP_SOLVED_INACCURATE : MPCQP_SOLVED;
   if (prim_inf) return approximate ? MPCQP_PRIMAL_INFEASIBLE_INACCURATE : MPCQP_PRIMAL_INFEASIBLE;
   if (dual_inf) return approximate ? MPCQP_DUAL_INFEASIBLE_INACCURATE : MPCQP_DUAL_INFEASIBLE;
@@ -1333,30 +1569,34 @@ __device__ __forceinline__ int check_termination(const KParams& p, Inst<RN, RM>&
 }
 
 // auxil.c compute_rho_estimate (residual vectors in scaled space)
-template <int RN, int RM>
+template <class Cx, int RN, int RM>
 __device__ __forceinline__ double rho_estimate(const KParams& p, const Inst<RN, RM>& S, const Resid<RN, RM>& R,
-                               int lane) {
+                                               double* v, Cx& C) {
   const DevPlan& P = p.pl;
+  const int lane = C.lane;
   double pr = 0.0, zn = 0.0, axn = 0.0, dr = 0.0, qn = 0.0, atn = 0.0, pxn = 0.0;
 #pragma unroll
   for (int r = 0; r < RM; ++r)
-    if (lane + 64 * r < P.m) {
+    if (lane + 64 * (r + C.zo) < P.m) {
       pr = dmaxd(pr, fabs(R.Ax[r] - S.z[r]));
       zn = dmaxd(zn, fabs(S.z[r]));
       axn = dmaxd(axn, fabs(R.Ax[r]));
     }
 #pragma unroll
   for (int r = 0; r < RN; ++r)
-    if (lane + 64 * r < P.n) {
+    if (lane + 64 * (r + C.xo) < P.n) {
       dr = dmaxd(dr, fabs((S.q[r] + R.Px[r]) + R.Aty[r]));
       qn = dmaxd(qn, fabs(S.q[r]));
       atn = dmaxd(atn, fabs(R.Aty[r]));
       pxn = dmaxd(pxn, fabs(R.Px[r]));
     }
-  pr = wave_max(pr), zn = wave_max(zn), axn = wave_max(axn);
-  dr = wave_max(dr), qn = wave_max(qn), atn = wave_max(atn), pxn = wave_max(pxn);
-  pr /= (dmaxd(zn, axn) + DIVISION_TOL);
-  dr /= (dmaxd(dmaxd(qn, atn), pxn) + DIVISION_TOL);
+  const double mine[7] = {wave_max(pr), wave_max(zn), wave_max(axn), wave_max(dr),
+                          wave_max(qn), wave_max(atn), wave_max(pxn)};
+  const bool ks[7] = {false, false, false, false, false, false, false};
+  double b[7];
+  C.template all<7>(p, v, mine, ks, b);
+  pr = b[0] / (dmaxd(b[1], b[2]) + DIVISION_TOL);
+  dr = b[3] / (dmaxd(dmaxd(b[4], b[5]), b[6]) + DIVISION_TOL);
   double est = S.rho * sqrt(pr / (dr + DIVISION_TOL));
   return dmind(dmaxd(est, RHO_MIN), RHO_MAX);
 }
@@ -1391,9 +1631,10 @@ __device__ __forceinline__ void scale_problem(const KParams& p, int inst, const 
   EllIdx<RN, ELL_KP> iP;
   EllIdx<RN, ELL_KAT> iAt;
   EllIdx<RM, ELL_KA> iA;
-  load_idx(P.eP, iP, lane);
-  load_idx(P.eAt, iAt, lane);
-  load_idx(P.eA, iA, lane);
+  const One C{lane, v};
+  load_idx(P.eP, iP, lane, 0);
+  load_idx(P.eAt, iAt, lane, 0);
+  load_idx(P.eA, iA, lane, 0);
   constexpr bool KF = RN == 2;
   const uint32_t kfP = KF ? ell_kflags<RN>(P.eP) : 0u, kfAt = KF ? ell_kflags<RN>(P.eAt) : 0u,
                  kfA = KF ? ell_kflags<RM>(P.eA) : 0u;
@@ -1445,13 +1686,13 @@ __device__ __forceinline__ void scale_problem(const KParams& p, int inst, const 
     double dp[RN], da[RN], er[RM], dt[RN], et[RM];
     T_BEGIN(t_s0);
     if (it == 0) {
-      ell_absmax_r<KF>(P.eP, iP, kfP, v, dp, lane);
+      ell_absmax_r<KF>(P.eP, iP, kfP, v, dp, C, 0);
     } else {
 #pragma unroll
       for (int r = 0; r < RN; ++r) dp[r] = cprev * dpc[r];
     }
-    ell_absmax_r<KF>(P.eAt, iAt, kfAt, v, da, lane);
-    ell_absmax_r<KF>(P.eA, iA, kfA, v, er, lane);
+    ell_absmax_r<KF>(P.eAt, iAt, kfAt, v, da, C, 0);
+    ell_absmax_r<KF>(P.eA, iA, kfA, v, er, C, 0);
     TSYNC(er[RM - 1]);
     T_END(T_SC0, t_s0);
     T_BEGIN(t_s1);
@@ -1486,7 +1727,7 @@ __device__ __forceinline__ void scale_problem(const KParams& p, int inst, const 
     T_END(T_SC2, t_s2);
     T_BEGIN(t_s3);
     // cost normalization: mean of P's column norms, |q|_inf
-    ell_absmax_r<KF>(P.eP, iP, kfP, v, dpc, lane);
+    ell_absmax_r<KF>(P.eP, iP, kfP, v, dpc, C, 0);
     // vec_mean of the column norms, summed in index order (staged in the D_temp slots: this
     // pass's factors are consumed) -- unless a tree sum shows it below |q|_inf by more than the
     // summation orders can differ (sum_slack; the norms are >= 0): then max(mean, |q|_inf) does
@@ -1539,15 +1780,13 @@ __device__ __forceinline__ void scale_problem(const KParams& p, int inst, const 
   unscale_p_r(v, P.S_P, P.nnzP, ra, ca, cinv, lane, Pw);
 }
 
-// end of scale_data: constraint classes, scaled bounds, D / E into the per-wave slab, and the
-// scaled values [P | A] copied from the scaling overlay into the resident MV region of the image
-// (read from there by the residual mat-vecs, certificates, KKT (re)assembly and the objective)
-template <int RN, int RM>
-__device__ __forceinline__ void scale_finish(const KParams& p, int inst, bool rebound, Inst<RN, RM>& S,
-                                             const Slab& sb, double* v, double* mvw, int lane,
-                                             const double (&D)[RN], const double (&E)[RM]) {
+// end of scale_data, the wave's slots: constraint classes, scaled bounds, D / E into the slab
+template <class Cx, int RN, int RM>
+__device__ __forceinline__ void scale_bounds(const KParams& p, int inst, bool rebound, Inst<RN, RM>& S,
+                                             const Slab& sb, const Cx& C, const double (&D)[RN],
+                                             const double (&E)[RM]) {
   const DevPlan& P = p.pl;
-  const int n = P.n, m = P.m;
+  const int n = P.n, m = P.m, lane = C.lane;
   S.cinv = 1. / S.c;
   // constraint classes (auxil.c set_rho_vec / update_rho_vec): after an update of A OSQP
   // classifies on bounds scaled by the PREVIOUS equilibration (update_bounds precedes the rescale
@@ -1557,7 +1796,7 @@ __device__ __forceinline__ void scale_finish(const KParams& p, int inst, bool re
   S.ct = 0;
 #pragma unroll
   for (int r = 0; r < RM; ++r) {
-    const int i = lane + 64 * r;
+    const int i = lane + 64 * (r + C.zo);
     const double ec = (rebound && i < m) ? Eold[i] : E[r];
     const double lc = S.l[r] * ec, uc = S.u[r] * ec;
     const uint32_t t = (lc < -thr && uc > thr) ? CT_FREE : ((uc - lc < RHO_TOL) ? CT_EQ : CT_INEQ);
@@ -1574,10 +1813,20 @@ __device__ __forceinline__ void scale_finish(const KParams& p, int inst, bool re
   }
 #pragma unroll
   for (int r = 0; r < RN; ++r) {
-    const int j = lane + 64 * r;
+    const int j = lane + 64 * (r + C.xo);
     S.Dinv[r] = 1. / D[r];
     if (j < n) sb.D[j] = D[r];
   }
+}
+// scale_bounds, and the scaled values [P | A] copied from the scaling overlay into the resident MV
+// region of the image (read from there by the residual mat-vecs, certificates, KKT (re)assembly
+// and the objective)
+template <int RN, int RM>
+__device__ __forceinline__ void scale_finish(const KParams& p, int inst, bool rebound, Inst<RN, RM>& S,
+                                             const Slab& sb, double* v, double* mvw, int lane,
+                                             const double (&D)[RN], const double (&E)[RM]) {
+  const DevPlan& P = p.pl;
+  scale_bounds(p, inst, rebound, S, sb, One{lane, mvw}, D, E);
   // the scaled values [P | A] stay resident in LDS (MV) for the residuals, certificates,
   // (re)assembly and objective; the scaling overlay they come from is overwritten by the KKT image
   LDS_FENCE();
@@ -1605,6 +1854,85 @@ __device__ __forceinline__ void scale_finish(const KParams& p, int inst, bool re
   if (P.mv_slab) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 }
 
+// The end of a solve: the objective (compute_obj_val), store_solution (NaN without a solution), the
+// warm-start state of the next solve and the info record.  Timing builds close the tail slot
+// (begun at t_tl, before the last checks) and flush the wave's slots in between, as before.
+#ifdef MPCQP_TIMING
+#define TTAIL_PARAM , unsigned long long* tacc, unsigned long long t_tl
+#define TTAIL_ARG(t) , tacc, t
+#else
+#define TTAIL_PARAM
+#define TTAIL_ARG(t)
+#endif
+template <class Cx, int RN, int RM>
+__device__ __forceinline__ void store_solution(const KParams& p, int inst, const Inst<RN, RM>& S,
+                                               const Slab& sb, double* v, Cx& C, int status, int iter,
+                                               int rho_updates TTAIL_PARAM) {
+  const DevPlan& P = p.pl;
+  const int n = P.n, m = P.m, lane = C.lane;
+  const bool sol = has_solution(status);
+  double obj = 0.0;
+  if (sol) {
+    double* xb = v + P.W;
+    const double* mv = C.mv(v);
+    LDS_FENCE();
+#pragma unroll
+    for (int r = 0; r < RN; ++r)
+      if (lane + 64 * (r + C.xo) < n) xb[lane + 64 * (r + C.xo)] = S.x[r];
+    C.sync(p, v);
+    double part = 0.0;
+    for (int k = C.tid(); k < P.nnzP; k += Cx::THREADS) {
+      const int i = P.Pi[k], j = P.Pcol[k];
+      const double pk = mv[P.MV + k];
+      part += (i == j) ? .5 * pk * xb[i] * xb[i] : pk * xb[i] * xb[j];
+    }
+#pragma unroll
+    for (int r = 0; r < RN; ++r)
+      if (lane + 64 * (r + C.xo) < n) part += S.q[r] * S.x[r];
+    obj = xch_sum(p, v, C, wave_sum(part)) * S.cinv;
+  } else if (status == MPCQP_PRIMAL_INFEASIBLE || status == MPCQP_PRIMAL_INFEASIBLE_INACCURATE) {
+    obj = OSQP_INFTY;
+  } else if (status == MPCQP_DUAL_INFEASIBLE || status == MPCQP_DUAL_INFEASIBLE_INACCURATE) {
+    obj = -OSQP_INFTY;
+  }
+  const double qnan = __builtin_nan("");
+#pragma unroll
+  for (int r = 0; r < RN; ++r) {
+    const int j = lane + 64 * (r + C.xo);
+    if (j < n) {
+      if (p.x_out) p.x_out[(size_t)inst * n + j] = sol ? sb.D[j] * S.x[r] : qnan;
+      p.xs[(size_t)inst * n + j] = sol ? S.x[r] : 0.0;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < RM; ++r) {
+    const int i = lane + 64 * (r + C.zo);
+    if (i < m) {
+      const double Ei = sb.E[i];
+      if (p.y_out) p.y_out[(size_t)inst * m + i] = sol ? (Ei * S.y[r]) * S.cinv : qnan;
+      p.zs[(size_t)inst * m + i] = sol ? S.z[r] : 0.0;
+      p.ys[(size_t)inst * m + i] = sol ? S.y[r] : 0.0;
+      p.Ecls[(size_t)inst * m + i] = Ei;
+    }
+  }
+  T_END(T_TAIL, t_tl);
+#ifdef MPCQP_TIMING
+  if (C.first() && p.timing)
+    for (int k = 0; k < T_NSLOT; ++k) atomicAdd(p.timing + k, tacc[k]);
+#endif
+  if (C.first()) {
+    p.rho_state[inst] = S.rho;
+    p.has_state[inst] = 1;
+    if (p.info.status) p.info.status[inst] = status;
+    if (p.info.iter) p.info.iter[inst] = iter;
+    if (p.info.rho_updates) p.info.rho_updates[inst] = rho_updates;
+    if (p.info.obj_val) p.info.obj_val[inst] = obj;
+    if (p.info.pri_res) p.info.pri_res[inst] = S.pri_res;
+    if (p.info.dua_res) p.info.dua_res[inst] = S.dua_res;
+    if (p.info.rho) p.info.rho[inst] = S.rho;
+  }
+}
+
 // Register buckets from which the per-lane addresses get an opaque lane id per instance (and per
 // check) instead of being hoisted out of the persistent instance loop: all of them (2).  Hoisted,
 // the addresses of the RN = 2 kernel held ~100 registers across the loop (256 + 154 allocated vs
@@ -1628,6 +1956,7 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
   const int n = P.n, m = P.m;
   const Slab sb = slab_of(P, scr);
   double* const mv = MVG ? sb.MV : v;
+  One W{lane, mv};  // the wave context of the shared check path
   Inst<RN, RM> S;
   const int hs = p.has_state[inst];
   const Drift dr = drift_of(p, inst);
@@ -1695,7 +2024,7 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
       if (lane + 64 * r < n) xb[lane + 64 * r] = S.x[r];
     LDS_FENCE();
     double az[RM];
-    ell_mv<RM, ELL_KA>(P.eA, mv, xb, az, lane, v + P.CACC);  // CSR row order
+    ell_mv<RM, ELL_KA>(P.eA, mv, xb, az, W, W.zo, W.stage(P, v));  // CSR row order
 #pragma unroll
     for (int r = 0; r < RM; ++r) S.z[r] = lane + 64 * r < m ? az[r] : 0.0;
     LDS_FENCE();
@@ -1904,22 +2233,23 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
     // RN = 4 the hoisted addresses spilled to scratch; MPCQP_OPAQUE_LANE_RN above)
     int clane = lane;
     if constexpr (RN >= MPCQP_OPAQUE_LANE_RN) asm volatile("" : "+v"(clane));
+    One C{clane, mv};
     if (can_check || adapt) {
       T_BEGIN(t_rs);
-      compute_residuals(p, S, R, sb, v, mv, clane TACC_ARG);
+      compute_residuals(p, S, R, v, C TACC_ARG);
       T_END(T_RESID, t_rs);
       T_COUNT(T_NCHK);
     }
     if (can_check) {
       T_BEGIN(t_tm);
-      status = check_termination(p, S, R, dy, dx, sb, v, mv, clane, false TACC_ARG);
+      status = check_termination(p, S, R, dy, dx, sb, v, C, false TACC_ARG);
       T_END(T_TERM, t_tm);
       if (status != 0) break;
       status = MPCQP_UNSOLVED;
     }
     T_BEGIN(t_ad);
     if (adapt) {
-      const double rho_new = rho_estimate(p, S, R, clane);
+      const double rho_new = rho_estimate(p, S, R, v, C);
       if (rho_new > S.rho * p.s.adaptive_rho_tolerance ||
           rho_new < S.rho / p.s.adaptive_rho_tolerance) {
         S.rho = dmind(dmaxd(rho_new, RHO_MIN), RHO_MAX);
@@ -1960,77 +2290,17 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
   T_BEGIN(t_tl);
   if (!can_check) {
     iter = iter - 1;
-    compute_residuals(p, S, R, sb, v, mv, lane TACC_ARG);
-    status = check_termination(p, S, R, dy, dx, sb, v, mv, lane, false TACC_ARG);
+    compute_residuals(p, S, R, v, W TACC_ARG);
+    status = check_termination(p, S, R, dy, dx, sb, v, W, false TACC_ARG);
     if (status == 0) status = MPCQP_UNSOLVED;
   }
   if (iter > p.s.max_iter) iter = p.s.max_iter;
   if (status == MPCQP_UNSOLVED) {
-    const int st = check_termination(p, S, R, dy, dx, sb, v, mv, lane, true TACC_ARG);
+    const int st = check_termination(p, S, R, dy, dx, sb, v, W, true TACC_ARG);
     status = st ? st : MPCQP_MAX_ITER_REACHED;
   }
 
-  // ---------------- objective (compute_obj_val) and store_solution
-  const bool sol = has_solution(status);
-  double obj = 0.0;
-  if (sol) {
-    double* xb = v + P.W;
-    LDS_FENCE();
-#pragma unroll
-    for (int r = 0; r < RN; ++r)
-      if (lane + 64 * r < n) xb[lane + 64 * r] = S.x[r];
-    LDS_FENCE();
-    double part = 0.0;
-    for (int k = lane; k < P.nnzP; k += 64) {
-      const int i = P.Pi[k], j = P.Pcol[k];
-      const double pk = mv[P.MV + k];
-      part += (i == j) ? .5 * pk * xb[i] * xb[i] : pk * xb[i] * xb[j];
-    }
-#pragma unroll
-    for (int r = 0; r < RN; ++r)
-      if (lane + 64 * r < n) part += S.q[r] * S.x[r];
-    obj = wave_sum(part) * S.cinv;
-  } else if (status == MPCQP_PRIMAL_INFEASIBLE || status == MPCQP_PRIMAL_INFEASIBLE_INACCURATE) {
-    obj = OSQP_INFTY;
-  } else if (status == MPCQP_DUAL_INFEASIBLE || status == MPCQP_DUAL_INFEASIBLE_INACCURATE) {
-    obj = -OSQP_INFTY;
-  }
-  const double qnan = __builtin_nan("");
-#pragma unroll
-  for (int r = 0; r < RN; ++r) {
-    const int j = lane + 64 * r;
-    if (j < n) {
-      if (p.x_out) p.x_out[(size_t)inst * n + j] = sol ? sb.D[j] * S.x[r] : qnan;
-      p.xs[(size_t)inst * n + j] = sol ? S.x[r] : 0.0;
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < RM; ++r) {
-    const int i = lane + 64 * r;
-    if (i < m) {
-      const double Ei = sb.E[i];
-      if (p.y_out) p.y_out[(size_t)inst * m + i] = sol ? (Ei * S.y[r]) * S.cinv : qnan;
-      p.zs[(size_t)inst * m + i] = sol ? S.z[r] : 0.0;
-      p.ys[(size_t)inst * m + i] = sol ? S.y[r] : 0.0;
-      p.Ecls[(size_t)inst * m + i] = Ei;
-    }
-  }
-  T_END(T_TAIL, t_tl);
-#ifdef MPCQP_TIMING
-  if (lane == 0 && p.timing)
-    for (int k = 0; k < T_NSLOT; ++k) atomicAdd(p.timing + k, tacc[k]);
-#endif
-  if (lane == 0) {
-    p.rho_state[inst] = S.rho;
-    p.has_state[inst] = 1;
-    if (p.info.status) p.info.status[inst] = status;
-    if (p.info.iter) p.info.iter[inst] = iter;
-    if (p.info.rho_updates) p.info.rho_updates[inst] = rho_updates;
-    if (p.info.obj_val) p.info.obj_val[inst] = obj;
-    if (p.info.pri_res) p.info.pri_res[inst] = S.pri_res;
-    if (p.info.dua_res) p.info.dua_res[inst] = S.dua_res;
-    if (p.info.rho) p.info.rho[inst] = S.rho;
-  }
+  store_solution(p, inst, S, sb, v, W, status, iter, rho_updates TTAIL_ARG(t_tl));
 }
 
 // One wave per workgroup; the instance image is the workgroup's whole (dynamic) LDS, at address 0.

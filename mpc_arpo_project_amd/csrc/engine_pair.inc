@@ -24,242 +24,14 @@
 // Barriers are s_waitcnt lgkmcnt(0) + s_barrier: only LDS is shared between the two waves (each
 // wave reads back only the global memory it wrote), so the step records' buffer loads stay in
 // flight across them.
-
-// LDS barrier of the two waves: this wave's LDS operations complete, then both meet
-#define BAR2()                                                                              \
-  do {                                                                                      \
-    LDS_FENCE();                                                                            \
-    __builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0); vmcnt and expcnt left at their max */ \
-    __builtin_amdgcn_s_barrier();                                                           \
-    LDS_FENCE();                                                                            \
-  } while (0)
-
-// BAR2_X(v, xid): the barrier of the diagnostic -DMPCQP_PAIR_CHECKS build -- an LDS-counter
-// barrier with a bounded wait instead of s_barrier, so a divergence of the two waves' barrier
-// sequences is reported (the hand-off check below sees the poison flag and sets the instance's
-// status to -1000) instead of hanging the GPU (VERDICT r05 item 6); the product build's BAR2.
-// Counters over the hand-off slot XID (4 doubles in checks builds): ints [4], [5] the barriers
-// waves 0 / 1 have reached, [6] the poison flag.
-#ifdef MPCQP_PAIR_CHECKS
-constexpr int PAIR_BAR_POLLS = 1 << 16;  // x s_sleep 4 (~256 cycles): ~17M cycles, far above any legit wait
-__device__ __noinline__ void bar2_checked(double* v, int xid) {
-  volatile int* ck = reinterpret_cast<volatile int*>(v + xid) + 4;
-  const int w = (int)(threadIdx.x >> 6);
-  LDS_FENCE();
-  __builtin_amdgcn_s_waitcnt(0xC07F);  // this wave's LDS operations complete
-  int mine = 0;
-  if ((threadIdx.x & 63) == 0) mine = ck[w] = ck[w] + 1;
-  mine = __builtin_amdgcn_readfirstlane(__shfl(mine, 0, 64));
-  for (int t = 0;; ++t) {
-    if (ck[2] != 0 || ck[1 - w] >= mine) break;
-    if (t >= PAIR_BAR_POLLS) {
-      if ((threadIdx.x & 63) == 0) ck[2] = 1;
-      break;
-    }
-    __builtin_amdgcn_s_sleep(4);
-  }
-  LDS_FENCE();
-}
-#define BAR2_X(v, xid) bar2_checked((v), (xid))
-// the test of the checked barrier itself (tests/test_gpu_pair_checks.py): when set (host:
-// mpcqp_debug_pair_inject), wave 1 of workgroup 0 skips one barrier -- the right-hand side's of the
-// first ADMM iteration of its first instance -- and the divergence must come back as status -1000
-__device__ int g_pair_inject = 0;
-#else
-#define BAR2_X(v, xid) BAR2()
-#endif
-
-// Where this wave sits: w (0 / 1), lane, its first n-slot xo and m-slot zo, the exchange buffer
-// phase (two buffers alternate, so a wave can write the next exchange while the other still reads
-// the last one: it cannot pass the barrier after that before the other wave has read)
-struct Wv {
-  int w, lane, xo, zo;
-  int ph;
-#ifdef MPCQP_PAIR_CHECKS
-  int nx;   // exchanges this wave made (diagnostic builds: both waves must agree at every hand-off)
-  int inj;  // this wave skips one barrier (g_pair_inject)
-#endif
-};
-
-// Cross-wave all-reduce of K wave-uniform values: out[k] = op_k(wave 0's, wave 1's)
-template <int K>
-__device__ __forceinline__ void xch_all(const KParams& p, double* v, Wv& W, const double (&mine)[K],
-                                        const bool (&is_sum)[K], double (&out)[K]) {
-  static_assert(K <= XCH_K, "exchange buffer");
-  double* buf = v + p.pl.XCH + W.ph * (2 * XCH_K);
-  if (W.lane == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) buf[W.w * XCH_K + k] = mine[k];
-  }
-  BAR2_X(v, p.pl.XID);
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const double a = buf[k], b = buf[XCH_K + k];
-    out[k] = is_sum[k] ? a + b : dmaxd(a, b);
-  }
-  W.ph ^= 1;
-#ifdef MPCQP_PAIR_CHECKS
-  W.nx++;
-#endif
-}
-__device__ __forceinline__ double xch_max(const KParams& p, double* v, Wv& W, double x) {
-  const double m[1] = {x};
-  const bool s[1] = {false};
-  double o[1];
-  xch_all<1>(p, v, W, m, s, o);
-  return o[0];
-}
-__device__ __forceinline__ double xch_sum(const KParams& p, double* v, Wv& W, double x) {
-  const double m[1] = {x};
-  const bool s[1] = {true};
-  double o[1];
-  xch_all<1>(p, v, W, m, s, o);
-  return o[0];
-}
-
-// ---- owner-split mat-vecs and norms (rows [off, off + R) of the ELL, long outputs by their owner)
-__device__ __forceinline__ bool owns(int o, int off, int R) { return o >= 64 * off && o < 64 * (off + R); }
-
-template <int R, int KMAX>
-__device__ __forceinline__ void ell_load2(const EllDev& e, EllTk<R, KMAX>& t, int lane, int off) {
-  static_assert(KMAX % 4 == 0, "lane-major term rows are loaded 16 bytes at a time");
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int rg = r + off;
-    if (e.K[rg] == 0) continue;
-    const uint4* row = reinterpret_cast<const uint4*>(e.pk + (size_t)(rg * 64 + lane) * KMAX);
-#pragma unroll
-    for (int q = 0; q < KMAX / 4; ++q) {
-      const uint4 w = row[q];
-      t.tk[r][4 * q] = w.x, t.tk[r][4 * q + 1] = w.y, t.tk[r][4 * q + 2] = w.z, t.tk[r][4 * q + 3] = w.w;
-    }
-  }
-#pragma unroll
-  for (int L = 0; L < ELL_LPF; ++L) {
-    t.lp[L] = 0, t.li[L] = 0;
-    if (L < e.nlong && owns(e.long_out[L], off, R) && lane < e.long_cnt[L]) {
-      const int q = e.long_off[L] + lane;
-      t.lp[L] = e.vpos[q], t.li[L] = e.in[q];
-    }
-  }
-}
-// stg: this wave's staging slots of the long outputs' products (seq_sum; ell_apply of the one-wave
-// kernel)
-template <int R, int KMAX>
-__device__ __forceinline__ void ell_apply2(const EllDev& e, const EllTk<R, KMAX>& t, const double* v,
-                                           const double* in, double (&out)[R], int lane, int off,
-                                           double* stg) {
-  constexpr int LPF = ELL_LPF;
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    double s = 0.0;
-    if (e.K[r + off] != 0) {
-      double a[KMAX], b[KMAX];
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k) a[k] = v[t.tk[r][k] & 0xffffu], b[k] = in[t.tk[r][k] >> 16];
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k) s += a[k] * b[k];
-    }
-    out[r] = s;
-  }
-  // this wave's long outputs: every one's products staged first (each at its own offset), then the
-  // sequential sums two at a time (ell_apply of the one-wave kernel)
-  int base = 0;
-  for (int L = 0; L < e.nlong; ++L) {
-    if (!owns(e.long_out[L], off, R)) continue;  // wave-uniform
-    int t0 = lane;
-#pragma unroll
-    for (int k = 0; k < LPF; ++k)
-      if (k == L) {
-        if (lane < e.long_cnt[L]) stg[base + lane] = v[t.lp[k]] * in[t.li[k]];
-        t0 = lane + 64;
-      }
-    for (int tt = t0; tt < e.long_cnt[L]; tt += 64) {
-      const int q = e.long_off[L] + tt;
-      stg[base + tt] = v[e.vpos[q]] * in[e.in[q]];
-    }
-    base += e.long_cnt[L];
-  }
-  if (base == 0) return;
-  LDS_FENCE();
-  auto put = [&](int o, double x) {
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-      if (o == lane + 64 * (r + off)) out[r] = x;
-  };
-  int po = -1, pc = 0, pb = 0;  // an owned output waiting for its partner chain
-  base = 0;
-  for (int L = 0; L < e.nlong; ++L) {
-    const int o = e.long_out[L], c = e.long_cnt[L];
-    if (!owns(o, off, R)) continue;
-    if (po < 0) {
-      po = o, pc = c, pb = base;
-    } else {
-      double s0, s1;
-      seq_sum2(stg + pb, pc, stg + base, c, s0, s1);
-      put(po, s0), put(o, s1);
-      po = -1;
-    }
-    base += c;
-  }
-  if (po >= 0) put(po, seq_sum(stg + pb, pc));
-  LDS_FENCE();
-}
-// the wave's half of the accumulator region C (free during the checks): its long outputs' staging
-__device__ __forceinline__ double* stage2(const DevPlan& P, double* v, const Wv& W) {
-  return v + P.CACC + W.w * (32 * P.NKS);
-}
-template <int R, int KMAX>
-__device__ __forceinline__ void ell_mv2(const EllDev& e, const double* v, const double* in,
-                                        double (&out)[R], const Wv& W, int off, double* stg) {
-  EllTk<R, KMAX> t;
-  ell_load2(e, t, W.lane, off);
-  ell_apply2(e, t, v, in, out, W.lane, off, stg);
-}
-template <int R, int KMAX>
-__device__ __forceinline__ void load_idx2(const EllDev& e, EllIdx<R, KMAX>& ix, int lane, int off) {
-  static_assert(KMAX % 4 == 0, "index rows are loaded 8 bytes at a time");
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int rg = r + off;
-    if (e.K[rg] == 0) continue;
-    const uint2* row = reinterpret_cast<const uint2*>(e.sk + (size_t)(rg * 64 + lane) * KMAX);
-#pragma unroll
-    for (int q = 0; q < KMAX / 4; ++q) {
-      const uint2 w = row[q];
-      ix.w[r][2 * q] = w.x, ix.w[r][2 * q + 1] = w.y;
-    }
-  }
-}
-template <int R, int KMAX>
-__device__ __forceinline__ void ell_absmax_r2(const EllDev& e, const EllIdx<R, KMAX>& ix,
-                                              const double* v, double (&out)[R], int lane, int off) {
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    double mx = 0.0;
-    if (e.K[r + off] != 0) {
-      double b[KMAX];
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k) {
-        const uint32_t w = ix.w[r][k / 2];
-        b[k] = v[(k & 1) ? (w >> 16) : (w & 0xffffu)];
-      }
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k) mx = dmaxd(fabs(b[k]), mx);
-    }
-    out[r] = mx;
-  }
-  for (int L = 0; L < e.nlong; ++L) {
-    const int o = e.long_out[L];
-    if (!owns(o, off, R)) continue;
-    double mx = 0.0;
-    for (int t = lane; t < e.long_cnt[L]; t += 64) mx = dmaxd(fabs(v[e.src[e.long_off[L] + t]]), mx);
-    mx = wave_max(mx);
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-      if (o == lane + 64 * (r + off)) out[r] = mx;
-  }
-}
+//
+// What this file holds is what only the two-wave kernel has: the half-record solve steps, the
+// owner-split factorization, Ruiz passes and MV copy (assemble_and_factor2, scale_problem2,
+// scale_finish2), the ADMM loop (solve_instance2) and the kernel.  The wave context Wv with its
+// barrier and exchange, and the check path -- ell_load / ell_apply / ell_mv / load_idx /
+// ell_absmax_r, compute_residuals, check_termination with both certificates, rho_estimate,
+// scale_bounds, store_solution -- are engine.hip's, written once over a wave context and called
+// here with Wv (there with One).
 
 // ---- solve steps of one wave: its half of the step record (segments 0 + 1 for wave 0, 2 + 3 for
 // wave 1) and its two targets
@@ -437,9 +209,9 @@ __device__ __forceinline__ void scale_problem2(const KParams& p, int inst, const
   EllIdx<RNH, ELL_KP> iP;
   EllIdx<RNH, ELL_KAT> iAt;
   EllIdx<RMH, ELL_KA> iA;
-  load_idx2(P.eP, iP, lane, W.xo);
-  load_idx2(P.eAt, iAt, lane, W.xo);
-  load_idx2(P.eA, iA, lane, W.zo);
+  load_idx(P.eP, iP, lane, W.xo);
+  load_idx(P.eAt, iAt, lane, W.xo);
+  load_idx(P.eA, iA, lane, W.zo);
   // this wave's half of the value overlay's rescale operand slots: value slots j in
   // [w 2 JWH, (w + 1) 2 JWH) (value k = 64 j + lane), u16 pairs
   constexpr int JWH = 2 * RNH * 2;  // = 4 RN / 2: the one-wave kernel's JW split in two
@@ -482,13 +254,13 @@ __device__ __forceinline__ void scale_problem2(const KParams& p, int inst, const
   for (int it = 0; it < p.s.scaling; ++it) {
     double dp[RNH], da[RNH], er[RMH], dt[RNH], et[RMH];
     if (it == 0) {
-      ell_absmax_r2(P.eP, iP, v, dp, lane, W.xo);
+      ell_absmax_r<false>(P.eP, iP, 0u, v, dp, W, W.xo);
     } else {
 #pragma unroll
       for (int r = 0; r < RNH; ++r) dp[r] = cprev * dpc[r];
     }
-    ell_absmax_r2(P.eAt, iAt, v, da, lane, W.xo);
-    ell_absmax_r2(P.eA, iA, v, er, lane, W.zo);
+    ell_absmax_r<false>(P.eAt, iAt, 0u, v, da, W, W.xo);
+    ell_absmax_r<false>(P.eA, iA, 0u, v, er, W, W.zo);
 #pragma unroll
     for (int r = 0; r < RNH; ++r) {
       const int j = lane + 64 * (r + W.xo);
@@ -536,7 +308,7 @@ __device__ __forceinline__ void scale_problem2(const KParams& p, int inst, const
     for (int r = 0; r < RMH; ++r) E[r] = E[r] * et[r];
     BAR2_X(v, p.pl.XID);  // the rescaled values before the cost normalisation's column norms (and the next
              // pass's factors are not written before every value of this pass is rescaled)
-    ell_absmax_r2(P.eP, iP, v, dpc, lane, W.xo);
+    ell_absmax_r<false>(P.eP, iP, 0u, v, dpc, W, W.xo);
     // vec_mean of the column norms in index order: both waves stage their columns in the D_temp
     // slots (consumed by the rescale above), the exchange's barrier publishes them
     double qmax = 0.0, csum = 0.0;
@@ -552,7 +324,7 @@ __device__ __forceinline__ void scale_problem2(const KParams& p, int inst, const
     const double mine[2] = {wave_sum(csum), wave_max(qmax)};
     const bool ks[2] = {true, false};
     double both[2];
-    xch_all<2>(p, v, W, mine, ks, both);  // its barrier publishes both waves' staged norms
+    W.all<2>(p, v, mine, ks, both);  // its barrier publishes both waves' staged norms
     const double inq = limit_scaling(both[1]), T = both[0];
     double c_temp = inq;  // the mean matters only above |q|_inf (scale_problem)
     if (!((T + sum_slack(T, n)) / n < inq)) {
@@ -599,292 +371,12 @@ __device__ __forceinline__ void scale_finish2(const KParams& p, int inst, bool r
                                               const Slab& sb, double* v, const Wv& W,
                                               const double (&D)[RNH], const double (&E)[RMH]) {
   const DevPlan& P = p.pl;
-  const int n = P.n, m = P.m, lane = W.lane, tid = lane + 64 * W.w;
-  S.cinv = 1. / S.c;
-  const double thr = OSQP_INFTY * MIN_SCALING;
-  const double* Eold = p.Ecls + (size_t)inst * m;
-  S.ct = 0;
-#pragma unroll
-  for (int r = 0; r < RMH; ++r) {
-    const int i = lane + 64 * (r + W.zo);
-    const double ec = (rebound && i < m) ? Eold[i] : E[r];
-    const double lc = S.l[r] * ec, uc = S.u[r] * ec;
-    const uint32_t t = (lc < -thr && uc > thr) ? CT_FREE : ((uc - lc < RHO_TOL) ? CT_EQ : CT_INEQ);
-    S.ct |= t << (2 * r);
-    const double eci = 1. / ec;  // warm: OSQP's E_old scaling, unscaling and the new E (scale_finish)
-    const double lb = rebound ? lc * eci : S.l[r], ub = rebound ? uc * eci : S.u[r];
-    S.l[r] = lb * E[r];
-    S.u[r] = ub * E[r];
-    S.Einv[r] = 1. / E[r];
-    if (i < m) sb.E[i] = E[r];
-  }
-#pragma unroll
-  for (int r = 0; r < RNH; ++r) {
-    const int j = lane + 64 * (r + W.xo);
-    S.Dinv[r] = 1. / D[r];
-    if (j < n) sb.D[j] = D[r];
-  }
+  const int tid = W.tid();
+  scale_bounds(p, inst, rebound, S, sb, W, D, E);
   const int cnt = P.nnzP + P.nnzA;
   for (int k = tid; k < cnt; k += 128) v[P.MV + k] = v[P.S_P + k];
   if (tid == 0) v[P.MVZ] = 0.0;
   BAR2_X(v, p.pl.XID);
-}
-
-// residuals, termination and certificates (one-wave kernel's versions, owner-split + exchanges)
-template <int RNH, int RMH>
-__device__ __forceinline__ void compute_residuals2(const KParams& p, Inst2<RNH, RMH>& S,
-                                                   Resid2<RNH, RMH>& R, double* v, Wv& W) {
-  const DevPlan& P = p.pl;
-  const int n = P.n, m = P.m, lane = W.lane;
-  double* xb = v + P.W;
-  double* yb = v + P.W + n;
-#pragma unroll
-  for (int r = 0; r < RNH; ++r) {
-    const int j = lane + 64 * (r + W.xo);
-    if (j < n) xb[j] = S.x[r];
-  }
-#pragma unroll
-  for (int r = 0; r < RMH; ++r) yb[lane + 64 * (r + W.zo)] = S.y[r];  // past m: W padding
-  BAR2_X(v, p.pl.XID);
-  {  // the three mat-vecs' index loads issued together (compute_residuals of the one-wave kernel)
-    EllTk<RMH, ELL_KA> tA;
-    EllTk<RNH, ELL_KP> tP;
-    EllTk<RNH, ELL_KAT> tT;
-    ell_load2(P.eA, tA, W.lane, W.zo);
-    ell_load2(P.eP, tP, W.lane, W.xo);
-    ell_load2(P.eAt, tT, W.lane, W.xo);
-    ell_apply2(P.eA, tA, v, xb, R.Ax, W.lane, W.zo, stage2(P, v, W));
-    ell_apply2(P.eP, tP, v, xb, R.Px, W.lane, W.xo, stage2(P, v, W));
-    ell_apply2(P.eAt, tT, v, yb, R.Aty, W.lane, W.xo, stage2(P, v, W));
-  }
-  double pr = 0.0, dr = 0.0;
-#pragma unroll
-  for (int r = 0; r < RMH; ++r) {
-    const int i = lane + 64 * (r + W.zo);
-    if (i < m) pr = dmaxd(pr, fabs(S.Einv[r] * (R.Ax[r] - S.z[r])));
-    if (i >= m) R.Ax[r] = 0.0;
-  }
-#pragma unroll
-  for (int r = 0; r < RNH; ++r) {
-    const int j = lane + 64 * (r + W.xo);
-    if (j < n) dr = dmaxd(dr, fabs(S.Dinv[r] * ((S.q[r] + R.Px[r]) + R.Aty[r])));
-    if (j >= n) R.Px[r] = 0.0, R.Aty[r] = 0.0;
-  }
-  const double mine[2] = {wave_max(pr), wave_max(dr)};
-  const bool ks[2] = {false, false};
-  double both[2];
-  xch_all<2>(p, v, W, mine, ks, both);  // also: every read of xb / yb done before anyone rewrites W
-  S.pri_res = both[0];
-  S.dua_res = S.cinv * both[1];
-}
-
-template <int RNH, int RMH>
-__device__ __forceinline__ bool is_primal_infeasible2(const KParams& p, Inst2<RNH, RMH>& S,
-                                                      double (&dy)[RMH], const double (&Ev)[RMH],
-                                                      double* v, Wv& W, double eps) {
-  const DevPlan& P = p.pl;
-  const int lane = W.lane;
-  const double thr = OSQP_INFTY * MIN_SCALING;
-  double nrm = 0.0, part = 0.0, apart = 0.0;
-  double* stg = v + P.CACC;  // lhs terms in index order (C: free during the checks)
-#pragma unroll
-  for (int r = 0; r < RMH; ++r) {
-    const int i = lane + 64 * (r + W.zo);
-    if (i < P.m) {
-      if (S.u[r] > thr)
-        dy[r] = (S.l[r] < -thr) ? 0.0 : dmind(dy[r], 0.0);
-      else if (S.l[r] < -thr)
-        dy[r] = dmaxd(dy[r], 0.0);
-      nrm = dmaxd(nrm, fabs(Ev[r] * dy[r]));
-      const double t = S.u[r] * dmaxd(dy[r], 0.0) + S.l[r] * dmind(dy[r], 0.0);
-      stg[i] = t;
-      part = part + t, apart = apart + fabs(t);
-    }
-  }
-  const double mine[3] = {wave_max(nrm), wave_sum(part), wave_sum(apart)};
-  const bool ks[3] = {false, true, true};
-  double b3[3];
-  xch_all<3>(p, v, W, mine, ks, b3);  // its barrier publishes both waves' staged terms
-  nrm = b3[0];
-  if (!(nrm > DIVISION_TOL)) return false;
-  // the decision on OSQP's sequential sum (seq_sum_lt), identical in both waves; the near-tie
-  // path reads the staged terms, so both waves meet before either stages in C again
-  const double sl = sum_slack(b3[2], P.m), th = eps * nrm;
-  bool lt = b3[1] + sl < th;
-  if (!lt && !(b3[1] - sl >= th)) {
-    lt = seq_sum(stg, P.m) < th;
-    BAR2_X(v, p.pl.XID);
-  }
-  if (!lt) return false;
-  double* yb = v + P.W + P.n;
-#pragma unroll
-  for (int r = 0; r < RMH; ++r) yb[lane + 64 * (r + W.zo)] = dy[r];
-  BAR2_X(v, p.pl.XID);
-  double aty[RNH];
-  ell_mv2<RNH, ELL_KAT>(P.eAt, v, yb, aty, W, W.xo, stage2(P, v, W));
-  double mx = 0.0;
-#pragma unroll
-  for (int r = 0; r < RNH; ++r)
-    if (lane + 64 * (r + W.xo) < P.n) mx = dmaxd(mx, fabs(aty[r] * S.Dinv[r]));
-  mx = xch_max(p, v, W, wave_max(mx));
-  return mx < eps * nrm;
-}
-
-template <int RNH, int RMH>
-__device__ __forceinline__ bool is_dual_infeasible2(const KParams& p, Inst2<RNH, RMH>& S,
-                                                    const double (&dx)[RNH], const double (&Dv)[RNH],
-                                                    double* v, Wv& W, double eps) {
-  const DevPlan& P = p.pl;
-  const int lane = W.lane;
-  const double thr = OSQP_INFTY * MIN_SCALING;
-  double nrm = 0.0, part = 0.0, apart = 0.0;
-  double* stg = v + P.CACC;  // q' dx in index order (vec_prod)
-#pragma unroll
-  for (int r = 0; r < RNH; ++r) {
-    const int j = lane + 64 * (r + W.xo);
-    if (j < P.n) {
-      nrm = dmaxd(nrm, fabs(Dv[r] * dx[r]));
-      const double t = S.q[r] * dx[r];
-      stg[j] = t;
-      part = part + t, apart = apart + fabs(t);
-    }
-  }
-  const double mine[3] = {wave_max(nrm), wave_sum(part), wave_sum(apart)};
-  const bool ks[3] = {false, true, true};
-  double b3[3];
-  xch_all<3>(p, v, W, mine, ks, b3);
-  nrm = b3[0];
-  if (!(nrm > DIVISION_TOL)) return false;
-  const double sl = sum_slack(b3[2], P.n), th = S.c * eps * nrm;
-  bool lt = b3[1] + sl < th;
-  if (!lt && !(b3[1] - sl >= th)) {
-    lt = seq_sum(stg, P.n) < th;
-    BAR2_X(v, p.pl.XID);
-  }
-  if (!lt) return false;
-  double* xb = v + P.W;
-#pragma unroll
-  for (int r = 0; r < RNH; ++r) {
-    const int j = lane + 64 * (r + W.xo);
-    if (j < P.n) xb[j] = dx[r];
-  }
-  BAR2_X(v, p.pl.XID);
-  double pdx[RNH];
-  ell_mv2<RNH, ELL_KP>(P.eP, v, xb, pdx, W, W.xo, stage2(P, v, W));
-  double mx = 0.0;
-#pragma unroll
-  for (int r = 0; r < RNH; ++r)
-    if (lane + 64 * (r + W.xo) < P.n) mx = dmaxd(mx, fabs(pdx[r] * S.Dinv[r]));
-  mx = xch_max(p, v, W, wave_max(mx));
-  if (!(mx < S.c * eps * nrm)) return false;
-  double adx[RMH];
-  ell_mv2<RMH, ELL_KA>(P.eA, v, xb, adx, W, W.zo, stage2(P, v, W));
-  int bad = 0;
-#pragma unroll
-  for (int r = 0; r < RMH; ++r) {
-    if (lane + 64 * (r + W.zo) < P.m) {
-      const double s = adx[r] * S.Einv[r];
-      if ((S.u[r] < thr && s > eps * nrm) || (S.l[r] > -thr && s < -eps * nrm)) bad = 1;
-    }
-  }
-  const double anybad = xch_max(p, v, W, __any(bad) ? 1.0 : 0.0);
-  return !(anybad > 0.0);
-}
-
-template <int RNH, int RMH>
-__device__ __forceinline__ int check_termination2(const KParams& p, Inst2<RNH, RMH>& S,
-                                                  const Resid2<RNH, RMH>& R, double (&dy)[RMH],
-                                                  const double (&dx)[RNH], const Slab& sb,
-                                                  double* v, Wv& W, bool approximate) {
-  const DevPlan& P = p.pl;
-  const int lane = W.lane;
-  double Ev[RMH], Dv[RNH];
-#pragma unroll
-  for (int r = 0; r < RMH; ++r) {
-    const int i = lane + 64 * (r + W.zo);
-    Ev[r] = i < P.m ? sb.E[i] : 0.0;
-  }
-#pragma unroll
-  for (int r = 0; r < RNH; ++r) {
-    const int j = lane + 64 * (r + W.xo);
-    Dv[r] = j < P.n ? sb.D[j] : 0.0;
-  }
-  double eps_abs = p.s.eps_abs, eps_rel = p.s.eps_rel;
-  double eps_pinf = p.s.eps_prim_inf, eps_dinf = p.s.eps_dual_inf;
-  if (approximate) eps_abs *= 10, eps_rel *= 10, eps_pinf *= 10, eps_dinf *= 10;
-  double zn = 0.0, axn = 0.0, qn = 0.0, atn = 0.0, pxn = 0.0;
-#pragma unroll
-  for (int r = 0; r < RMH; ++r) {
-    const int i = lane + 64 * (r + W.zo);
-    if (i < P.m) {
-      const double ei = S.Einv[r];
-      zn = dmaxd(zn, fabs(ei * S.z[r]));
-      axn = dmaxd(axn, fabs(ei * R.Ax[r]));
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < RNH; ++r) {
-    const int j = lane + 64 * (r + W.xo);
-    if (j < P.n) {
-      const double di = S.Dinv[r];
-      qn = dmaxd(qn, fabs(di * S.q[r]));
-      atn = dmaxd(atn, fabs(di * R.Aty[r]));
-      pxn = dmaxd(pxn, fabs(di * R.Px[r]));
-    }
-  }
-  const double mine[5] = {wave_max(zn), wave_max(axn), wave_max(qn), wave_max(atn), wave_max(pxn)};
-  const bool ks[5] = {false, false, false, false, false};
-  double both[5];
-  xch_all<5>(p, v, W, mine, ks, both);
-  zn = both[0], axn = both[1], qn = both[2], atn = both[3], pxn = both[4];
-  const double eps_prim = eps_abs + eps_rel * dmaxd(zn, axn);
-  const double eps_dual = eps_abs + eps_rel * (dmaxd(dmaxd(qn, atn), pxn) * S.cinv);
-  bool prim_ok = false, dual_ok = false, prim_inf = false, dual_inf = false;
-  if (S.pri_res < eps_prim)
-    prim_ok = true;
-  else
-    prim_inf = is_primal_infeasible2(p, S, dy, Ev, v, W, eps_pinf);
-  if (S.dua_res < eps_dual)
-    dual_ok = true;
-  else
-    dual_inf = is_dual_infeasible2(p, S, dx, Dv, v, W, eps_dinf);
-  BAR2_X(v, p.pl.XID);  // the certificates' staging in W read by both waves before anyone rewrites W
-  if (prim_ok && dual_ok) return approximate ? MPCQP_SOLVED_INACCURATE : MPCQP_SOLVED;
-  if (prim_inf) return approximate ? MPCQP_PRIMAL_INFEASIBLE_INACCURATE : MPCQP_PRIMAL_INFEASIBLE;
-  if (dual_inf) return approximate ? MPCQP_DUAL_INFEASIBLE_INACCURATE : MPCQP_DUAL_INFEASIBLE;
-  return 0;
-}
-
-template <int RNH, int RMH>
-__device__ __forceinline__ double rho_estimate2(const KParams& p, const Inst2<RNH, RMH>& S,
-                                                const Resid2<RNH, RMH>& R, double* v, Wv& W) {
-  const DevPlan& P = p.pl;
-  const int lane = W.lane;
-  double pr = 0.0, zn = 0.0, axn = 0.0, dr = 0.0, qn = 0.0, atn = 0.0, pxn = 0.0;
-#pragma unroll
-  for (int r = 0; r < RMH; ++r)
-    if (lane + 64 * (r + W.zo) < P.m) {
-      pr = dmaxd(pr, fabs(R.Ax[r] - S.z[r]));
-      zn = dmaxd(zn, fabs(S.z[r]));
-      axn = dmaxd(axn, fabs(R.Ax[r]));
-    }
-#pragma unroll
-  for (int r = 0; r < RNH; ++r)
-    if (lane + 64 * (r + W.xo) < P.n) {
-      dr = dmaxd(dr, fabs((S.q[r] + R.Px[r]) + R.Aty[r]));
-      qn = dmaxd(qn, fabs(S.q[r]));
-      atn = dmaxd(atn, fabs(R.Aty[r]));
-      pxn = dmaxd(pxn, fabs(R.Px[r]));
-    }
-  const double mine[7] = {wave_max(pr), wave_max(zn), wave_max(axn), wave_max(dr),
-                          wave_max(qn), wave_max(atn), wave_max(pxn)};
-  const bool ks[7] = {false, false, false, false, false, false, false};
-  double b[7];
-  xch_all<7>(p, v, W, mine, ks, b);
-  pr = b[0] / (dmaxd(b[1], b[2]) + DIVISION_TOL);
-  dr = b[3] / (dmaxd(dmaxd(b[4], b[5]), b[6]) + DIVISION_TOL);
-  double est = S.rho * sqrt(pr / (dr + DIVISION_TOL));
-  return dmind(dmaxd(est, RHO_MIN), RHO_MAX);
 }
 
 // MODE: 0 the solve steps split between the waves (Plan::split_steps), 1 the same with the matrix
@@ -954,7 +446,7 @@ __device__ __forceinline__ void solve_instance2(const KParams& p, int inst, doub
       if (lane + 64 * (r + W.xo) < n) xb[lane + 64 * (r + W.xo)] = S.x[r];
     BAR2_X(v, p.pl.XID);
     double az[RMH];
-    ell_mv2<RMH, ELL_KA>(P.eA, v, xb, az, W, W.zo, stage2(P, v, W));
+    ell_mv<RMH, ELL_KA>(P.eA, v, xb, az, W, W.zo, W.stage(P, v));
 #pragma unroll
     for (int r = 0; r < RMH; ++r) S.z[r] = lane + 64 * (r + W.zo) < m ? az[r] : 0.0;
     BAR2_X(v, p.pl.XID);
@@ -1181,11 +673,11 @@ __device__ __forceinline__ void solve_instance2(const KParams& p, int inst, doub
     asm volatile("" : "+v"(C.lane));
     if (can_check || adapt) {
       BAR2_X(v, p.pl.XID);  // every wave's solution reads of W done before the residual staging rewrites it
-      compute_residuals2(p, S, R, v, C);
+      compute_residuals(p, S, R, v, C TACC_ARG);
       T_COUNT(T_NCHK);
     }
     if (can_check) {
-      status = check_termination2(p, S, R, dy, dx, sb, v, C, false);
+      status = check_termination(p, S, R, dy, dx, sb, v, C, false TACC_ARG);
       if (status != 0) {
         W.ph = C.ph;  // the exchange buffer phase carries on
         break;
@@ -1193,7 +685,7 @@ __device__ __forceinline__ void solve_instance2(const KParams& p, int inst, doub
       status = MPCQP_UNSOLVED;
     }
     if (adapt) {
-      const double rho_new = rho_estimate2(p, S, R, v, C);
+      const double rho_new = rho_estimate(p, S, R, v, C);
       if (rho_new > S.rho * p.s.adaptive_rho_tolerance ||
           rho_new < S.rho / p.s.adaptive_rho_tolerance) {
         S.rho = dmind(dmaxd(rho_new, RHO_MIN), RHO_MAX);
@@ -1217,76 +709,17 @@ __device__ __forceinline__ void solve_instance2(const KParams& p, int inst, doub
   if (!can_check) {
     iter = iter - 1;
     BAR2_X(v, p.pl.XID);
-    compute_residuals2(p, S, R, v, W);
-    status = check_termination2(p, S, R, dy, dx, sb, v, W, false);
+    compute_residuals(p, S, R, v, W TACC_ARG);
+    status = check_termination(p, S, R, dy, dx, sb, v, W, false TACC_ARG);
     if (status == 0) status = MPCQP_UNSOLVED;
   }
   if (iter > p.s.max_iter) iter = p.s.max_iter;
   if (status == MPCQP_UNSOLVED) {
-    const int st = check_termination2(p, S, R, dy, dx, sb, v, W, true);
+    const int st = check_termination(p, S, R, dy, dx, sb, v, W, true TACC_ARG);
     status = st ? st : MPCQP_MAX_ITER_REACHED;
   }
 
-  // ---------------- objective and store_solution
-  const bool sol = has_solution(status);
-  double obj = 0.0;
-  if (sol) {
-    double* xb = v + P.W;
-#pragma unroll
-    for (int r = 0; r < RNH; ++r)
-      if (lane + 64 * (r + W.xo) < n) xb[lane + 64 * (r + W.xo)] = S.x[r];
-    BAR2_X(v, p.pl.XID);
-    double part = 0.0;
-    for (int k = lane + 64 * W.w; k < P.nnzP; k += 128) {
-      const int i = P.Pi[k], j = P.Pcol[k];
-      const double pk = v[P.MV + k];
-      part += (i == j) ? .5 * pk * xb[i] * xb[i] : pk * xb[i] * xb[j];
-    }
-#pragma unroll
-    for (int r = 0; r < RNH; ++r)
-      if (lane + 64 * (r + W.xo) < n) part += S.q[r] * S.x[r];
-    obj = xch_sum(p, v, W, wave_sum(part)) * S.cinv;
-  } else if (status == MPCQP_PRIMAL_INFEASIBLE || status == MPCQP_PRIMAL_INFEASIBLE_INACCURATE) {
-    obj = OSQP_INFTY;
-  } else if (status == MPCQP_DUAL_INFEASIBLE || status == MPCQP_DUAL_INFEASIBLE_INACCURATE) {
-    obj = -OSQP_INFTY;
-  }
-  const double qnan = __builtin_nan("");
-#pragma unroll
-  for (int r = 0; r < RNH; ++r) {
-    const int j = lane + 64 * (r + W.xo);
-    if (j < n) {
-      if (p.x_out) p.x_out[(size_t)inst * n + j] = sol ? sb.D[j] * S.x[r] : qnan;
-      p.xs[(size_t)inst * n + j] = sol ? S.x[r] : 0.0;
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < RMH; ++r) {
-    const int i = lane + 64 * (r + W.zo);
-    if (i < m) {
-      const double Ei = sb.E[i];
-      if (p.y_out) p.y_out[(size_t)inst * m + i] = sol ? (Ei * S.y[r]) * S.cinv : qnan;
-      p.zs[(size_t)inst * m + i] = sol ? S.z[r] : 0.0;
-      p.ys[(size_t)inst * m + i] = sol ? S.y[r] : 0.0;
-      p.Ecls[(size_t)inst * m + i] = Ei;
-    }
-  }
-  T_END(T_TAIL, t_tl);
-#ifdef MPCQP_TIMING
-  if (W.w == 0 && lane == 0 && p.timing)
-    for (int k = 0; k < T_NSLOT; ++k) atomicAdd(p.timing + k, tacc[k]);
-#endif
-  if (W.w == 0 && lane == 0) {
-    p.rho_state[inst] = S.rho;
-    p.has_state[inst] = 1;
-    if (p.info.status) p.info.status[inst] = status;
-    if (p.info.iter) p.info.iter[inst] = iter;
-    if (p.info.rho_updates) p.info.rho_updates[inst] = rho_updates;
-    if (p.info.obj_val) p.info.obj_val[inst] = obj;
-    if (p.info.pri_res) p.info.pri_res[inst] = S.pri_res;
-    if (p.info.dua_res) p.info.dua_res[inst] = S.dua_res;
-    if (p.info.rho) p.info.rho[inst] = S.rho;
-  }
+  store_solution(p, inst, S, sb, v, W, status, iter, rho_updates TTAIL_ARG(t_tl));
   BAR2_X(v, p.pl.XID);  // the image is rewritten by the next instance's scaling
 }
 
