@@ -21,6 +21,9 @@
  *                                     res.x[(Nx+1)*nx:(Nx+1)*nx+nu] and res.info.status
  *                                     reference src/trajectorySimulate.py:296-314,
  *                                               src/trajectorySimulateC.py:338-356
+ *   mpcqp_update_settings          <- prob.update_settings(max_iter=, eps_abs=, ...)
+ *                                     [osqp_update_max_iter, osqp_update_eps_abs, ...]
+ *   mpcqp_update_rho               <- prob.update_settings(rho=)  [osqp_update_rho]
  *   mpcqp_warm_start               <- prob.warm_start(x=, y=)  [osqp_warm_start]
  *   mpcqp_destroy                  <- object destruction  [osqp_cleanup]
  *
@@ -28,13 +31,16 @@
  * sparsity pattern of P and A; A values and the bounds l, u are per instance.  The cost data (the
  * values of P, and q) are shared by the batch with mpcqp_set_data / mpcqp_update_lin_cost /
  * mpcqp_update_P and per instance with their _batched forms (e.g. one weight set per instance of a
- * tuning sweep); each P_i must be positive semidefinite, which is not checked.  B = 1 is the
- * reference's use.
+ * tuning sweep); each P_i must be positive semidefinite, which is not checked.  The solver settings
+ * are those given to mpcqp_create for every instance, or a row per instance
+ * (mpcqp_set_settings_batched, mpcqp_update_settings_batched, mpcqp_update_rho_batched).  B = 1 is
+ * the reference's use.
  *
  * Rules
  *   - every function returns 0 on success and a negative MPCQP_E* code on failure; nothing throws
  *     across the ABI; mpcqp_last_error() gives a message for the calling thread;
- *   - structure arrays (mpcqp_structure) are HOST pointers read during mpcqp_create only;
+ *   - structure arrays (mpcqp_structure) are HOST pointers read during mpcqp_create only; settings
+ *     (mpcqp_settings, one or an array of B) are HOST pointers read during the call;
  *   - every data pointer is a DEVICE pointer owned by the caller (e.g. a torch tensor's
  *     data_ptr()), laid out row-major [instance][element], float64 / int32;
  *   - work is enqueued on the HIP stream given to mpcqp_create and is asynchronous with respect to
@@ -117,6 +123,46 @@ int mpcqp_set_data(mpcqp_handle *h, const double *Px, const double *q, const dou
  * a later plain mpcqp_set_data returns it to one shared row. */
 int mpcqp_set_data_batched(mpcqp_handle *h, const double *Px, const double *q, const double *Ax,
                            const double *l, const double *u);
+
+/* Solver settings per instance, and the osqp_update_<setting> family.  Every settings array here is
+ * a HOST pointer, validated by mpcqp_create's rules (a failing row is named: "row 17: invalid
+ * settings"; polish / scaled_termination set: MPCQP_E_UNSUPPORTED, naming the field), copied into
+ * handle-owned storage and uploaded on the handle's stream: the caller may free it on return.  A
+ * call that fails leaves the handle's settings as they were.  Each of these calls (mpcqp_check_settings
+ * and mpcqp_get_settings apart) synchronises the handle's stream before it returns -- the staging
+ * of the upload is reused -- so it costs a host synchronisation and must not be made while the
+ * stream is being captured into a graph: change settings between captures.  The device rows are allocated at the
+ * first batched call; a handle that never makes one runs on the settings given to mpcqp_create.
+ *
+ * mpcqp_check_settings: host-only, validates `count` rows.
+ * mpcqp_set_settings_batched: set-up settings, rows [B], every field counts.  sigma, scaling and rho
+ *   change the scaling and the factorization, so this is a set-up operation: the handle returns to
+ *   its state after mpcqp_create (no data, no warm-start state, no scaling) and a solve, update or
+ *   warm start before the next mpcqp_set_data[_batched] returns MPCQP_E_NODATA.  A cold instance
+ *   starts from its own row's rho, clipped to [1e-6, 1e6].
+ * mpcqp_update_settings[_batched]: the fields OSQP can update between solves -- max_iter, eps_abs,
+ *   eps_rel, eps_prim_inf, eps_dual_inf, alpha, check_termination, warm_start (delta and
+ *   polish_refine_iter are stored and unused; polish and scaled_termination must be 0).  The
+ *   set-up fields rho, sigma, scaling, adaptive_rho, adaptive_rho_interval and
+ *   adaptive_rho_tolerance of the argument are IGNORED: the handle keeps its own.  Iterates,
+ *   carried rho and data scaling are kept; legal before mpcqp_set_data.  The shared form on a
+ *   handle that holds rows writes those fields into every row.  An automatic
+ *   adaptive_rho_interval (0) follows the check_termination in force at each solve.
+ * mpcqp_update_rho[_batched]: osqp_update_rho, one value or rho [B] (host).  rho <= 0 is
+ *   MPCQP_E_INVALID; otherwise the setting and the carried rho of every instance (never solved and
+ *   warm-started ones too) become the value clipped to [1e-6, 1e6] -- mpcqp_get_settings then
+ *   reports the clipped value, where mpcqp_create and mpcqp_set_settings_batched keep rho as given
+ *   and clip only what the kernels read; the iterates are kept.  The
+ *   engine refactors at every solve, so nothing else is needed.
+ * mpcqp_get_settings: the settings currently in force, rows [B] (host). */
+int mpcqp_check_settings(const mpcqp_settings *rows, int32_t count);
+int mpcqp_set_settings_batched(mpcqp_handle *h, const mpcqp_settings *rows);
+int mpcqp_update_settings(mpcqp_handle *h, const mpcqp_settings *s);
+int mpcqp_update_settings_batched(mpcqp_handle *h, const mpcqp_settings *rows);
+int mpcqp_update_rho(mpcqp_handle *h, double rho);
+int mpcqp_update_rho_batched(mpcqp_handle *h, const double *rho);
+int mpcqp_get_settings(const mpcqp_handle *h, mpcqp_settings *rows);
+
 /* New bounds for every instance [B*m] (device).  Alone (no mpcqp_update_A before the next solve)
  * this is osqp_update_bounds: the instance keeps its data scaling D, E, c -- the next solve re-runs
  * the Ruiz passes on the same unscaled data as the last scaling did, bitwise the same factors --

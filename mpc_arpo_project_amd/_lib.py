@@ -51,9 +51,20 @@ EXPORTED = (
     "mpcqp_kernel_info",
     "mpcqp_set_data_batched", "mpcqp_update_lin_cost_batched", "mpcqp_update_P",
     "mpcqp_update_P_batched", "mpcqp_cl_set_id_period",
+    "mpcqp_check_settings", "mpcqp_set_settings_batched", "mpcqp_update_settings",
+    "mpcqp_update_settings_batched", "mpcqp_update_rho", "mpcqp_update_rho_batched",
+    "mpcqp_get_settings",
     "mpcqp_cl_create", "mpcqp_cl_destroy", "mpcqp_cl_configure", "mpcqp_cl_step",
     "mpcqp_cl_set_ids", "mpcqp_cl_set_tracking", "mpcqp_cl_noise", "mpcqp_cl_set_plant", "mpcqp_clc_period",
     "mpcqp_ukf_create", "mpcqp_ukf_destroy", "mpcqp_ukf_step", "mpcqp_plant_rk45",
+)
+
+# entry points a diagnostic library of an earlier revision (MPCQP_LIBRARY) may lack: white-box
+# hooks and the per-instance settings family, which a handle with plain shared settings never calls
+PREDATED = (
+    "mpcqp_get_scaling", "mpcqp_check_settings", "mpcqp_set_settings_batched",
+    "mpcqp_update_settings", "mpcqp_update_settings_batched", "mpcqp_update_rho",
+    "mpcqp_update_rho_batched", "mpcqp_get_settings",
 )
 
 STATUS = {
@@ -143,7 +154,7 @@ def lib():
     def _sig(L, name, what, value):
         fn = getattr(L, name, None)
         if fn is None:
-            if host_only or (diag_lib and name in ("mpcqp_get_scaling",)):
+            if host_only or (diag_lib and name in PREDATED):
                 return
             raise MPCQPError(f"{LIB_PATH} does not export {name}")
         setattr(fn, what, value)
@@ -155,6 +166,14 @@ def lib():
     _sig(L, "mpcqp_destroy", "argtypes", [vp])
     _sig(L, "mpcqp_set_data", "argtypes", [vp, dp, dp, dp, dp, dp])
     _sig(L, "mpcqp_set_data_batched", "argtypes", [vp, dp, dp, dp, dp, dp])
+    sp = C.POINTER(Settings)
+    _sig(L, "mpcqp_check_settings", "argtypes", [sp, i32])
+    _sig(L, "mpcqp_set_settings_batched", "argtypes", [vp, sp])
+    _sig(L, "mpcqp_update_settings", "argtypes", [vp, sp])
+    _sig(L, "mpcqp_update_settings_batched", "argtypes", [vp, sp])
+    _sig(L, "mpcqp_update_rho", "argtypes", [vp, C.c_double])
+    _sig(L, "mpcqp_update_rho_batched", "argtypes", [vp, C.POINTER(C.c_double)])
+    _sig(L, "mpcqp_get_settings", "argtypes", [vp, sp])
     _sig(L, "mpcqp_update_bounds", "argtypes", [vp, dp, dp])
     _sig(L, "mpcqp_update_A", "argtypes", [vp, dp])
     _sig(L, "mpcqp_update_lin_cost", "argtypes", [vp, dp])
@@ -231,6 +250,59 @@ def default_settings(**overrides) -> Settings:
             raise ValueError(f"unknown setting '{k}'")
         setattr(s, k, type(getattr(s, k))(v))
     return s
+
+
+def _setting_key(k):
+    if k == "warm_starting":  # OSQP 1.x spelling
+        k = "warm_start"
+    if not any(k == f[0] for f in Settings._fields_):
+        raise ValueError(f"unknown setting '{k}'")
+    return k
+
+
+def per_instance(settings: dict) -> bool:
+    """Whether any value of a settings dict is given per instance (a sequence, not a scalar)."""
+    import numpy as np
+
+    return any(np.ndim(v) > 0 for k, v in settings.items() if k != "verbose")
+
+
+def settings_rows(B: int, **kw):
+    """A (Settings * B) array for the per-instance entry points: the defaults, with each value of
+    kw a scalar (every row) or a length-B sequence (one per row).  A sequence of another length is
+    a ValueError naming the key."""
+    rows = (Settings * int(B))()
+    view = rows_view(rows)
+    view[:] = rows_view((Settings * 1)(default_settings()))[0]
+    for k, v in kw.items():
+        if k != "verbose":
+            view[_setting_key(k)] = setting_column(B, k, v)
+    return rows
+
+
+def rows_view(rows):
+    """A numpy structured view (no copy) of a (Settings * B) array: view[name] is the column of B
+    values, so whole columns are read and written at once whatever the batch size."""
+    import numpy as np
+
+    return np.frombuffer(rows, dtype=np.dtype(Settings))
+
+
+def setting_column(B: int, k: str, v):
+    """The value(s) of setting k for B rows: a scalar, or a length-B sequence (checked)."""
+    import numpy as np
+
+    if np.ndim(v) == 0:
+        return v
+    col = np.asarray(v).reshape(-1)
+    if col.size != B:
+        raise ValueError(f"setting '{k}' has {col.size} values for a batch of {B}")
+    return col
+
+
+def check_settings(rows) -> None:
+    """mpcqp_check_settings on a (Settings * count) array (host only)."""
+    check(lib().mpcqp_check_settings(rows, len(rows)), "mpcqp_check_settings")
 
 
 def analyze(P_triu_csc, A_csc):

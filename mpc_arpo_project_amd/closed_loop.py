@@ -339,6 +339,20 @@ def shard_streams(device, S):
     return have[:S]
 
 
+def shard_settings(kw, B, a, b):
+    """kw with every per-instance solver setting (a length-B sequence under a settings name) cut
+    to the chasers [a, b) of one shard -- as the shards cut `variant`; everything else as given"""
+    names = {f[0] for f in _lib.Settings._fields_} | {"warm_starting"}
+    out = dict(kw)
+    for k, v in kw.items():
+        if k in names and np.ndim(v) > 0:
+            v = np.asarray(v).reshape(-1)
+            if v.size != B:
+                raise ValueError(f"setting '{k}' has {v.size} values for a batch of {B}")
+            out[k] = v[a:b]
+    return out
+
+
 class ShardedClosedLoop:
     """A BatchClosedLoop split into S shards of consecutive chasers, each on its own HIP stream.
 
@@ -385,7 +399,7 @@ class ShardedClosedLoop:
             self.parts.append(BatchClosedLoop(prob, x0[self.cut[j]:self.cut[j + 1]], device=dev,
                                               id_offset=id_offset + self.cut[j], stream=sts[j],
                                               noise_source=shard_source(j), **shard_variant(j),
-                                              **kw))
+                                              **shard_settings(kw, B, self.cut[j], self.cut[j + 1])))
         torch.cuda.synchronize(dev)
 
     def step(self):
@@ -560,7 +574,8 @@ class ShardedClosedLoopC:
         sts = shard_streams(dev, S) if S > 1 else [None]
         self.parts = [BatchClosedLoopC(prob, x0[self.cut[j]:self.cut[j + 1]], T_cont, T_final,
                                        mean_motion, device=dev, id_offset=id_offset + self.cut[j],
-                                       stream=sts[j], noise_source=shard_source(j), **kw)
+                                       stream=sts[j], noise_source=shard_source(j),
+                                       **shard_settings(kw, B, self.cut[j], self.cut[j + 1]))
                       for j in range(S)]
         self.B = B
         self.schedule = self.parts[0].schedule

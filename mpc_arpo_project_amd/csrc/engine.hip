@@ -24,6 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mpcqp.h"
@@ -57,7 +58,11 @@ namespace {
 // ------------------------------------------------------------------------------------- device
 struct KParams {
   DevPlan pl;
-  mpcqp_settings s;
+  // the solver settings: one row shared by every instance (stride 0) or a row per instance ([B],
+  // stride sizeof(mpcqp_settings) bytes: mpcqp_set_settings_batched); set_row.  rho of a row is
+  // already clipped to [RHO_MIN, RHO_MAX] on the host
+  const mpcqp_settings* srows;
+  int sstride;
   int B;
   // set-up data: one row shared by every instance (stride 0) or a row per instance ([B][nnzP] /
   // [B][n], strides nnzP / n: mpcqp_set_data_batched); setup_row
@@ -85,10 +90,6 @@ struct KParams {
   double* scratch;  // [grid][nnzP + nnzA] scaled P and A values of the wave's current instance
   unsigned int* counter;
   unsigned long long* timing;  // diagnostic builds only (MPCQP_TIMING): cycles per phase
-  // initial rho of a cold instance, min(max(settings.rho, RHO_MIN), RHO_MAX), computed on the host:
-  // read per instance from the kernel arguments instead of a loop-invariant register (the gfx950
-  // backend of ROCm 7.2 was seen to spill such a hoisted double and reload only its low half)
-  double rho0;
   const int32_t* skip;  // [B] or null: instances with skip[i] != 0 are not solved (outputs kept)
   const int32_t* order;  // [B] or null: the k-th instance handed out is order[k] (mpcqp_set_order)
 };
@@ -121,6 +122,34 @@ __device__ __forceinline__ DriftSel drift_sel(const KParams& p, int inst) {
 // Wave-uniform: scalar address arithmetic, the product in 64 bits
 __device__ __forceinline__ const double* setup_row(const double* base, int stride, int inst) {
   return base + (size_t)inst * (size_t)stride;
+}
+// the settings row of instance inst (KParams::srows with its stride; 0: the shared row), in the
+// constant address space: its fields are read with scalar loads, as the kernel arguments are (the
+// two-wave kernel's reads before its ADMM loop, and the Ruiz pass count).  Indexed by the instance
+// id (not by the position in the hand-out order), which is wave-uniform but not provably so to the
+// compiler: values that have to stay in SGPRs go through uniform_i / uniform_d at their use.  The
+// initial rho of a cold instance is read from the row per instance, not kept in a loop-invariant
+// register (the gfx950 backend of ROCm 7.2 was seen to spill such a hoisted double and reload only
+// its low half)
+typedef const __attribute__((address_space(4))) mpcqp_settings* SetRow;
+__device__ __forceinline__ SetRow set_row(const KParams& p, int inst) {
+  // the stride in bytes, the offset in 32 bits (the host refuses a table beyond 4 GiB)
+  return (SetRow)((uintptr_t)p.srows + (uint32_t)inst * (uint32_t)p.sstride);
+}
+// The row at a use inside or behind the ADMM loop (the check blocks).  The loop holds the instance
+// id in a VGPR (vector_id, formed before the loop) and the row is addressed from an opaque copy of
+// it: the fields are read with vector loads and made uniform at their use (uniform_d), and neither
+// the pointer nor the loaded values are hoisted out of the loop.  So the check blocks add nothing to
+// the SGPRs live across an iteration (tests/test_isa_hot_loops.py: the non-check iteration's spill
+// reloads) and one VGPR
+__device__ __forceinline__ uint32_t vector_id(int inst) {
+  uint32_t vi = (uint32_t)inst;
+  asm volatile("" : "+v"(vi));
+  return vi;
+}
+__device__ __forceinline__ const mpcqp_settings* set_row_at_use(const KParams& p, uint32_t vinst) {
+  asm volatile("" : "+v"(vinst));
+  return (const mpcqp_settings*)((const char*)p.srows + (size_t)(vinst * (uint32_t)p.sstride));
 }
 // the drift buffers' rows of instance inst: P values (cnt = nnzP, base p.Pw) or q (n, p.qw)
 __device__ __forceinline__ double* drift_row(double* base, int b, int B, int cnt, int inst) {
@@ -206,6 +235,45 @@ __device__ __forceinline__ void swap32_d(double x, double& a, double& b) {
 __device__ __forceinline__ double uniform_d(double x) {
   return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)),
                           __builtin_amdgcn_readfirstlane(__double2loint(x)));
+}
+__device__ __forceinline__ int uniform_i(int x) { return __builtin_amdgcn_readfirstlane(x); }
+// What the check blocks read of the instance's row: the four tolerances of check_termination and
+// adaptive_rho_tolerance.  HELD: loaded once per instance before the ADMM loop and kept in VGPRs
+// across it (ten registers), made uniform at each use -- no memory access in a check block, as when
+// the settings were kernel arguments; the (2, 4) one-wave kernels, which have the registers.
+// Otherwise the instance id in a VGPR, and the fields are loaded where they are used
+// (set_row_at_use): the (4, 8) bucket and the two-wave kernel, at their register budget.
+template <bool HELD>
+struct RowTol;
+template <>
+struct RowTol<false> {
+  uint32_t vinst;
+};
+template <>
+struct RowTol<true> {
+  double eps_abs, eps_rel, eps_pinf, eps_dinf, ar_tol;
+};
+__device__ __forceinline__ RowTol<true> hold_tol(const mpcqp_settings* sr) {
+  RowTol<true> t{sr->eps_abs, sr->eps_rel, sr->eps_prim_inf, sr->eps_dual_inf, sr->adaptive_rho_tolerance};
+  asm volatile("" : "+v"(t.eps_abs), "+v"(t.eps_rel), "+v"(t.eps_pinf), "+v"(t.eps_dinf), "+v"(t.ar_tol));
+  return t;
+}
+template <bool HELD>
+__device__ __forceinline__ void tol_eps(const KParams& p, const RowTol<HELD>& t, double& eps_abs,
+                                        double& eps_rel, double& eps_pinf, double& eps_dinf) {
+  if constexpr (HELD) {
+    eps_abs = uniform_d(t.eps_abs), eps_rel = uniform_d(t.eps_rel);
+    eps_pinf = uniform_d(t.eps_pinf), eps_dinf = uniform_d(t.eps_dinf);
+  } else {
+    const mpcqp_settings* sr = set_row_at_use(p, t.vinst);
+    eps_abs = uniform_d(sr->eps_abs), eps_rel = uniform_d(sr->eps_rel);
+    eps_pinf = uniform_d(sr->eps_prim_inf), eps_dinf = uniform_d(sr->eps_dual_inf);
+  }
+}
+template <bool HELD>
+__device__ __forceinline__ double tol_adaptive_rho(const KParams& p, const RowTol<HELD>& t) {
+  if constexpr (HELD) return uniform_d(t.ar_tol);
+  else return uniform_d(set_row_at_use(p, t.vinst)->adaptive_rho_tolerance);
 }
 // Wave all-reductions: DPP butterflies inside each 16-lane row (partners exchange and combine the
 // same two operands, so every lane of a row holds the bitwise-identical row result), then the row
@@ -1259,7 +1327,8 @@ struct Resid {
 // (OSQP kkt.c form_KKT / update_KKT_*), then factorize.
 template <int RN, int RM>
 __device__ __forceinline__ void assemble_and_factor(const KParams& p, const Slab& sb, double* v,
-                                                    const double* mv, int lane, const Inst<RN, RM>& S) {
+                                                    const double* mv, int lane, const Inst<RN, RM>& S,
+                                                    double sigma) {
   const DevPlan& P = p.pl;
   for (int k = lane; k < P.nnzL; k += 64) v[P.LX + k] = 0.0;
   // the whole 1/D region (the D_j tasks' KKT diagonal in, 1/D_j out; 0 in the padding, which the
@@ -1272,11 +1341,11 @@ __device__ __forceinline__ void assemble_and_factor(const KParams& p, const Slab
     v[P.MONE] = -1.0;
   }
   LDS_FENCE();
-  for (int j = lane; j < P.n; j += 64) v[P.slotSig[j]] = p.s.sigma;
+  for (int j = lane; j < P.n; j += 64) v[P.slotSig[j]] = sigma;
   LDS_FENCE();
   for (int k = lane; k < P.nnzP; k += 64) {
     const double val = mv[P.MV + k];
-    v[P.slotP[k]] = (P.Pi[k] == P.Pcol[k]) ? val + p.s.sigma : val;
+    v[P.slotP[k]] = (P.Pi[k] == P.Pcol[k]) ? val + sigma : val;
   }
   for (int k = lane; k < P.nnzA; k += 64) v[P.slotA[k]] = mv[P.MV + P.nnzP + k];
 #pragma unroll
@@ -1494,10 +1563,11 @@ __device__ __forceinline__ bool is_dual_infeasible(const KParams& p, Inst<RN, RM
   return !(xch_max(p, v, C, __any(bad) ? 1.0 : 0.0) > 0.0);
 }
 
-template <class Cx, int RN, int RM>
-__device__ __forceinline__ int check_termination(const KParams& p, Inst<RN, RM>& S, const Resid<RN, RM>& R,
-                                                 double (&dy)[RM], const double (&dx)[RN], const Slab& sb,
-                                                 double* v, Cx& C, bool approximate TACC_PARAM) {
+template <class Cx, int RN, int RM, bool HELD>
+__device__ __forceinline__ int check_termination(const KParams& p, const RowTol<HELD>& tol, Inst<RN, RM>& S,
+                                                 const Resid<RN, RM>& R, double (&dy)[RM],
+                                                 const double (&dx)[RN], const Slab& sb, double* v,
+                                                 Cx& C, bool approximate TACC_PARAM) {
   T_BEGIN(t_m0);
   const DevPlan& P = p.pl;
   const int lane = C.lane;
@@ -1513,8 +1583,9 @@ __device__ __forceinline__ int check_termination(const KParams& p, Inst<RN, RM>&
     const int j = lane + 64 * (r + C.xo);
     Dv[r] = j < P.n ? sb.D[j] : 0.0;
   }
-  double eps_abs = p.s.eps_abs, eps_rel = p.s.eps_rel;
-  double eps_pinf = p.s.eps_prim_inf, eps_dinf = p.s.eps_dual_inf;
+  // the instance's tolerances, read here where they are used (not held across the ADMM loop)
+  double eps_abs, eps_rel, eps_pinf, eps_dinf;
+  tol_eps(p, tol, eps_abs, eps_rel, eps_pinf, eps_dinf);
   if (approximate) eps_abs *= 10, eps_rel *= 10, eps_pinf *= 10, eps_dinf *= 10;
   // compute_pri_tol / compute_dua_tol (unscaled termination)
   double zn = 0.0, axn = 0.0, qn = 0.0, atn = 0.0, pxn = 0.0;
@@ -1672,7 +1743,8 @@ __device__ __forceinline__ void scale_problem(const KParams& p, int inst, const 
   double cprev = 1.0;  // cost factor of the last pass, not yet applied to P's values
   double dpc[RN];      // P's column norms before that factor (the cost normalisation's)
   LDS_FENCE();
-  for (int it = 0; it < p.s.scaling; ++it) {
+  const int scaling = uniform_i(set_row(p, inst)->scaling);
+  for (int it = 0; it < scaling; ++it) {
     // (4, 8) bucket: the passes' operand addresses recomputed in every pass (hoisted out of the
     // pass loop they held ~190 registers: that kernel's register peak, MPCQP_MAX_KERNEL_REGS)
     if constexpr (RN >= 4) {
@@ -1979,11 +2051,14 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
     T_END(T_SCFIN, t_sf);
   }
   T_END(T_SCALE, t_sc);
-  S.rho = (hs != 0) ? p.rho_state[inst] : p.rho0;
+  // before the loop too the row is read with vector loads (set_row_at_use): a scalar row pointer
+  // held from here to the loop cost the loop's non-check iteration spill reloads
+  const mpcqp_settings* sr = set_row_at_use(p, vector_id(inst));
+  S.rho = (hs != 0) ? p.rho_state[inst] : sr->rho;
   set_rho(S);
   T_BEGIN(t_f0);
   MatRegs M;  // KM_MREG: the solve steps' matrix operands of the current factorization
-  assemble_and_factor<RN, RM>(p, sb, v, mv, lane, S);
+  assemble_and_factor<RN, RM>(p, sb, v, mv, lane, S, sr->sigma);
   if constexpr (MREG) {
     LDS_FENCE();
     load_mats(P.fwdm, P.nfwd, (uint32_t)lane, v, M.m[0]);
@@ -1993,7 +2068,7 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
   T_COUNT(T_NFACT);
 
   // ---------------- warm start
-  const bool warm = p.s.warm_start && hs != 0;
+  const bool warm = uniform_i(sr->warm_start) && hs != 0;
   if (warm && hs == 1) {
 #pragma unroll
     for (int r = 0; r < RN; ++r) {
@@ -2073,15 +2148,22 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
   };
   // loop constants held in VGPRs (an opaque copy: otherwise they are re-read from the kernel
   // arguments inside the loop, with an lgkmcnt(0) wait that also drains the LDS queue)
-  double sigma = p.s.sigma, alpha = p.s.alpha, alpha_c = 1.0 - p.s.alpha;
+  double sigma = sr->sigma, alpha = sr->alpha, alpha_c = 1.0 - sr->alpha;
   asm volatile("" : "+v"(sigma), "+v"(alpha), "+v"(alpha_c));
-  const int chk = p.s.check_termination;
-  int ar_int = p.s.adaptive_rho_interval;
-  if (p.s.adaptive_rho && ar_int == 0) ar_int = chk ? 4 * chk : 100;
-  if (!p.s.adaptive_rho) ar_int = 0;
+  // the instance's own row, read once here before the loop; the values the loop tests go through
+  // readfirstlane, so the "+s" pins below get SGPRs although the instance id is not provably uniform
+  const int chk = uniform_i(sr->check_termination);
+  int ar_int = uniform_i(sr->adaptive_rho_interval);
+  const int ar_on = uniform_i(sr->adaptive_rho);
+  if (ar_on && ar_int == 0) ar_int = chk ? 4 * chk : 100;
+  if (!ar_on) ar_int = 0;
   int chk_left = chk, ar_left = ar_int;  // iterations to the next check / rho adaptation
   int status = MPCQP_UNSOLVED, iter = 0, rho_updates = 0;
-  bool can_check = false;
+  // (4, 8) bucket: the check / adapt decisions as 32-bit flags made uniform (readfirstlane), not
+  // lane masks: a mask is an SGPR pair, spilled and reloaded on every iteration of that kernel (11
+  // reloads on its non-check iteration against 25 with masks; tests/test_isa_hot_loops.py)
+  using Flag = std::conditional_t<(RN >= 4), int, bool>;
+  Flag can_check = false;
   double dx[RN], dy[RM];
   Resid<RN, RM> R;
   Pipe<SolveOps<PAIRED>> sp;
@@ -2096,6 +2178,15 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
   // carried pipeline: the step counts as opaque SGPR values, like the loop bounds below
   int nfwd_s = P.nfwd, nbwd_s = P.nbwd;
   if constexpr (CARRY) asm volatile("" : "+s"(nfwd_s), "+s"(nbwd_s));
+  // (4, 8) bucket: the step counts held in VGPRs and made uniform at the solves (a readfirstlane
+  // each), not re-read from the kernel arguments there: with the loop's scalar registers as they
+  // are now that kernel would rematerialise them with an s_load on every iteration
+  int nfwd_v = P.nfwd, nbwd_v = P.nbwd;
+  if constexpr (RN >= 4) asm volatile("" : "+v"(nfwd_v), "+v"(nbwd_v));
+  auto steps_of = [&](int nv, int ns) {
+    if constexpr (RN >= 4) return uniform_i(nv);
+    else return ns;
+  };
   // the diagonal pass's 1/D in registers between factorizations ((2, 4) bucket: 12 VGPRs; six
   // LDS reads fewer per iteration)
   constexpr bool DREG = RN == 2 && !MREG;
@@ -2110,7 +2201,17 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
   load_dinv(lane);
   // the loop bounds as opaque SGPR values: not rematerialised from the kernel arguments at the
   // loop head (an s_load whose lgkmcnt(0) wait also drains the LDS queue, every iteration)
-  int max_iter = p.s.max_iter;
+  int max_iter = uniform_i(sr->max_iter);
+  // the check blocks' tolerances (RowTol), and the iteration bound for behind the loop
+  constexpr bool HELD = CARRY;
+  RowTol<HELD> tol;
+  int max_iter_v = max_iter;
+  if constexpr (HELD) {
+    tol = hold_tol(sr);
+    asm volatile("" : "+v"(max_iter_v));
+  } else {
+    tol.vinst = vector_id(inst);
+  }
   int chk_s = chk, ar_s = ar_int;
   asm volatile("" : "+s"(max_iter), "+s"(chk_s), "+s"(ar_s));
   // a carried pipeline (RP_CARRY) enters every iteration with forward steps 0 and 1 in flight in
@@ -2155,7 +2256,7 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
     else if constexpr (CARRY)  // leaves backward steps 0 and 1 in sets a and b
       run_body_carry<PAIRED>(rs_fwd, 0, nfwd_s, (uint32_t)lane, v, sp);
     else
-      run_body(rs_fwd, P.nfwd, (uint32_t)lane, sops, sp);
+      run_body(rs_fwd, steps_of(nfwd_v, P.nfwd), (uint32_t)lane, sops, sp);
     T_END(T_FWD, t_fw);
     T_BEGIN(t_v1);
     if constexpr (MREG)  // lands during the diagonal pass
@@ -2192,7 +2293,7 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
     else if constexpr (CARRY)  // leaves forward steps 0 and 1 (the pad copy) in sets a and b
       run_body_carry<PAIRED>(rs_fwd, nfwd_s, nbwd_s, (uint32_t)lane, v, sp);
     else
-      run_body(rs_bwd, P.nbwd, (uint32_t)lane, sops, sp);
+      run_body(rs_bwd, steps_of(nbwd_v, P.nbwd), (uint32_t)lane, sops, sp);
     T_END(T_BWD, t_bw);
     T_BEGIN(t_v2);
     // x, z, y updates (auxil.c update_x / update_z / update_y).  The solution reads are issued
@@ -2225,8 +2326,10 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
     T_END(T_V2, t_v2);
     T_BEGIN(t_ck);
     can_check = chk_s && --chk_left == 0;  // iter % chk == 0
+    if constexpr (RN >= 4) can_check = uniform_i(can_check);
     if (can_check) chk_left = chk_s;
-    const bool adapt = ar_s && --ar_left == 0;  // iter % ar_int == 0
+    Flag adapt = ar_s && --ar_left == 0;  // iter % ar_int == 0
+    if constexpr (RN >= 4) adapt = uniform_i(adapt);
     if (adapt) ar_left = ar_s;
     // the check-time code gets an opaque copy of the lane id: its per-lane addresses are
     // recomputed at each check instead of being hoisted out of the ADMM loop into registers (at
@@ -2242,7 +2345,7 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
     }
     if (can_check) {
       T_BEGIN(t_tm);
-      status = check_termination(p, S, R, dy, dx, sb, v, C, false TACC_ARG);
+      status = check_termination(p, tol, S, R, dy, dx, sb, v, C, false TACC_ARG);
       T_END(T_TERM, t_tm);
       if (status != 0) break;
       status = MPCQP_UNSOLVED;
@@ -2250,14 +2353,14 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
     T_BEGIN(t_ad);
     if (adapt) {
       const double rho_new = rho_estimate(p, S, R, v, C);
-      if (rho_new > S.rho * p.s.adaptive_rho_tolerance ||
-          rho_new < S.rho / p.s.adaptive_rho_tolerance) {
+      const double ar_tol = tol_adaptive_rho(p, tol);
+      if (rho_new > S.rho * ar_tol || rho_new < S.rho / ar_tol) {
         S.rho = dmind(dmaxd(rho_new, RHO_MIN), RHO_MAX);
         set_rho(S);
         rho_updates++;
         LDS_FENCE();
         T_BEGIN(t_f1);
-        assemble_and_factor<RN, RM>(p, sb, v, mv, clane, S);
+        assemble_and_factor<RN, RM>(p, sb, v, mv, clane, S, sigma);
         if constexpr (MREG) {
           LDS_FENCE();
           load_mats(P.fwdm, P.nfwd, (uint32_t)clane, v, M.m[0]);
@@ -2291,12 +2394,19 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
   if (!can_check) {
     iter = iter - 1;
     compute_residuals(p, S, R, v, W TACC_ARG);
-    status = check_termination(p, S, R, dy, dx, sb, v, W, false TACC_ARG);
+    status = check_termination(p, tol, S, R, dy, dx, sb, v, W, false TACC_ARG);
     if (status == 0) status = MPCQP_UNSOLVED;
   }
-  if (iter > p.s.max_iter) iter = p.s.max_iter;
+  {
+    // the carried-pipeline kernel takes the bound from its VGPR copy, the others keep its SGPR past
+    // the loop: per kernel, the form that leaves the non-check iteration within its spill reloads of
+    // before (register allocation; tests/test_isa_hot_loops.py)
+    int cap = max_iter;
+    if constexpr (CARRY) cap = uniform_i(max_iter_v);
+    if (iter > cap) iter = cap;
+  }
   if (status == MPCQP_UNSOLVED) {
-    const int st = check_termination(p, S, R, dy, dx, sb, v, W, true TACC_ARG);
+    const int st = check_termination(p, tol, S, R, dy, dx, sb, v, W, true TACC_ARG);
     status = st ? st : MPCQP_MAX_ITER_REACHED;
   }
 
@@ -2480,7 +2590,14 @@ bool record_carry(const Plan& pl, const DevImage& img) {
 
 struct mpcqp_handle {
   Plan plan;
+  // the settings in force: `set` for every instance, or `rows` [B] once a batched settings call was
+  // made (mpcqp_set_settings_batched / mpcqp_update_settings_batched / mpcqp_update_rho_batched).
+  // The kernels read the device copies (KParams::srows): d_set, one row, from mpcqp_create on;
+  // d_rows [B], allocated at the first batched call.  `stage` is the host side of the uploads
   mpcqp_settings set;
+  std::vector<mpcqp_settings> rows;
+  mpcqp_settings *d_set = nullptr, *d_rows = nullptr;
+  std::vector<char> stage;
   int B = 0;
   hipStream_t stream = nullptr;
   std::vector<void*> owned;  // every device allocation of the handle (dev_alloc; mpcqp_destroy)
@@ -2545,6 +2662,71 @@ static SetupRows setup_rows(const mpcqp_handle* h, bool batched) {
   return batched ? SetupRows{h->PxB, h->qB, h->plan.nnzP, h->plan.n} : SetupRows{h->Px, h->q, 0, 0};
 }
 
+static double clip_rho(double rho) { return std::min(std::max(rho, RHO_MIN), RHO_MAX); }
+// count elements from handle-owned host storage (h->stage) to the device on the handle's stream;
+// returns once the copy is done, so the staging may be rewritten by the next call
+template <typename T>
+static int upload(mpcqp_handle* h, T* dst, size_t count) {
+  HIPCHK(hipMemcpyAsync(dst, h->stage.data(), sizeof(T) * count, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+// the settings in force to their device copy (KParams::srows): rho of a row clipped to
+// [RHO_MIN, RHO_MAX], the initial rho of a cold instance
+static int upload_settings(mpcqp_handle* h) {
+  const bool per_inst = !h->rows.empty();
+  const size_t cnt = per_inst ? (size_t)h->B : 1;
+  h->stage.resize(cnt * sizeof(mpcqp_settings));
+  mpcqp_settings* st = (mpcqp_settings*)h->stage.data();
+  for (size_t i = 0; i < cnt; ++i) {
+    st[i] = per_inst ? h->rows[i] : h->set;
+    st[i].rho = clip_rho(st[i].rho);
+  }
+  return upload(h, per_inst ? h->d_rows : h->d_set, cnt);
+}
+// The host settings of a handle before an entry point changes them.  A call that fails after that
+// point -- an upload -- puts them back and, best effort, their device copy with them, so that
+// mpcqp_get_settings and the kernels go on agreeing and a failed call changes nothing
+struct SettingsBackup {
+  mpcqp_handle* h;
+  mpcqp_settings set;
+  std::vector<mpcqp_settings> rows;
+  explicit SettingsBackup(mpcqp_handle* h_) : h(h_), set(h_->set), rows(h_->rows) {}
+  int restore(int rc) {
+    const std::string msg = mpcqp_last_error();
+    h->set = set;
+    h->rows.swap(rows);
+    (void)upload_settings(h);
+    return set_error(rc, msg);
+  }
+};
+// a handle with shared settings moves to a row per instance holding the same values (the device
+// rows are allocated here, at the first batched settings call; the caller uploads)
+static int settings_rows(mpcqp_handle* h) {
+  if ((uint64_t)h->B * sizeof(mpcqp_settings) > 0xffffffffull)  // set_row's 32-bit offset
+    return set_error(MPCQP_E_UNSUPPORTED, "batch too large for per-instance settings rows");
+  if (!h->d_rows && !dev_alloc(h, h->d_rows, sizeof(mpcqp_settings) * (size_t)h->B))
+    return set_error(MPCQP_E_HIP, "hipMalloc(per-instance settings rows)");
+  if (h->rows.empty()) h->rows.assign((size_t)h->B, h->set);
+  return 0;
+}
+// the fields osqp_update_<setting> can change, from `from` into `to`
+static void merge_updatable(mpcqp_settings& to, const mpcqp_settings& from) {
+  to.max_iter = from.max_iter, to.eps_abs = from.eps_abs, to.eps_rel = from.eps_rel;
+  to.eps_prim_inf = from.eps_prim_inf, to.eps_dual_inf = from.eps_dual_inf, to.alpha = from.alpha;
+  to.check_termination = from.check_termination, to.warm_start = from.warm_start;
+  to.delta = from.delta, to.polish_refine_iter = from.polish_refine_iter;  // stored, unused
+}
+// the row an update leaves: the current one with the updatable fields of `from`; validated as
+// mpcqp_create validates (polish / scaled_termination of `from` refused)
+static int merged_row(const mpcqp_settings& cur, const mpcqp_settings& from, int row,
+                      mpcqp_settings& out) {
+  out = cur;
+  merge_updatable(out, from);
+  out.polish = from.polish, out.scaled_termination = from.scaled_termination;
+  return check_settings_row(out, row);
+}
+
 extern "C" {
 
 int mpcqp_create(const mpcqp_structure* st, const mpcqp_settings* s, int32_t batch, void* stream,
@@ -2552,12 +2734,7 @@ int mpcqp_create(const mpcqp_structure* st, const mpcqp_settings* s, int32_t bat
   if (!st || !s || !out || batch <= 0) return set_error(MPCQP_E_INVALID, "invalid argument");
   *out = nullptr;
   if (st->m <= 0) return set_error(MPCQP_E_UNSUPPORTED, "problems without constraints (m == 0)");
-  if (s->polish) return set_error(MPCQP_E_UNSUPPORTED, "polish is not implemented in this build");
-  if (s->scaled_termination)
-    return set_error(MPCQP_E_UNSUPPORTED, "scaled_termination is not implemented in this build");
-  if (s->max_iter <= 0 || s->alpha <= 0 || s->alpha >= 2 || s->sigma <= 0 || s->rho <= 0 ||
-      s->scaling < 0 || s->check_termination < 0 || s->eps_abs < 0 || s->eps_rel < 0)
-    return set_error(MPCQP_E_INVALID, "invalid settings");
+  if (int rc = check_settings_row(*s)) return rc;
   mpcqp_handle* h = new mpcqp_handle();
   // every failure from here on destroys the handle (msg by value: it may live in the handle)
   auto fail = [h](int code, std::string msg) { return mpcqp_destroy(h), set_error(code, msg); };
@@ -2631,8 +2808,9 @@ int mpcqp_create(const mpcqp_structure* st, const mpcqp_settings* s, int32_t bat
                   dev_alloc(h, h->pend, I * Bz) && dev_alloc(h, h->rho, D * Bz) &&
                   dev_alloc(h, h->has_state, I * Bz) &&
                   dev_alloc(h, h->scratch, D * (size_t)h->grid * slab_doubles(pl.n, pl.m, pl.mv_slab)) &&
-                  dev_alloc(h, h->counter, 64);
+                  dev_alloc(h, h->counter, 64) && dev_alloc(h, h->d_set, sizeof(mpcqp_settings));
   if (!ok) return fail(MPCQP_E_HIP, "hipMalloc(batch buffers)");
+  if (int rc = upload_settings(h)) return fail(rc, mpcqp_last_error());
   if (hipMemset(h->has_state, 0, I * Bz) != hipSuccess || hipMemsetD32(h->dsel, -2, Bz) != hipSuccess ||
       hipMemset(h->pend, 0, I * Bz) != hipSuccess)
     return fail(MPCQP_E_HIP, "hipMemset");
@@ -2700,6 +2878,90 @@ int mpcqp_set_data(mpcqp_handle* h, const double* Px, const double* q, const dou
 int mpcqp_set_data_batched(mpcqp_handle* h, const double* Px, const double* q, const double* Ax,
                            const double* l, const double* u) {
   return set_data(h, true, Px, q, Ax, l, u);
+}
+
+int mpcqp_set_settings_batched(mpcqp_handle* h, const mpcqp_settings* rows) {
+  if (int rc = guard(h, rows)) return rc;
+  if (int rc = mpcqp_check_settings(rows, h->B)) return rc;  // nothing changed so far
+  SettingsBackup old(h);
+  if (int rc = settings_rows(h)) return rc;
+  h->rows.assign(rows, rows + h->B);
+  if (int rc = upload_settings(h)) return old.restore(rc);
+  // a new set-up (sigma, scaling and rho change the scaling and the factorization): the state
+  // after mpcqp_create, data to be given again
+  const size_t B = (size_t)h->B;
+  HIPCHK(hipMemsetAsync(h->has_state, 0, sizeof(int32_t) * B, h->stream));
+  HIPCHK(hipMemsetD32Async(h->dsel, -2, B, h->stream));
+  HIPCHK(hipMemsetAsync(h->pend, 0, sizeof(int32_t) * B, h->stream));
+  h->has_data = false;
+  h->batched = false;
+  return 0;
+}
+
+int mpcqp_update_settings(mpcqp_handle* h, const mpcqp_settings* s) {
+  if (int rc = guard(h, s)) return rc;
+  SettingsBackup old(h);
+  if (h->rows.empty()) {
+    mpcqp_settings next;
+    if (int rc = merged_row(h->set, *s, -1, next)) return rc;
+    h->set = next;
+  } else {  // the same fields into every row
+    mpcqp_settings next;
+    for (int i = 0; i < h->B; ++i)
+      if (int rc = merged_row(h->rows[i], *s, i, next)) return rc;
+    for (int i = 0; i < h->B; ++i) merge_updatable(h->rows[i], *s);
+  }
+  if (int rc = upload_settings(h)) return old.restore(rc);
+  return 0;
+}
+
+int mpcqp_update_settings_batched(mpcqp_handle* h, const mpcqp_settings* rows) {
+  if (int rc = guard(h, rows)) return rc;
+  mpcqp_settings next;
+  for (int i = 0; i < h->B; ++i)
+    if (int rc = merged_row(h->rows.empty() ? h->set : h->rows[i], rows[i], i, next)) return rc;
+  SettingsBackup old(h);
+  if (int rc = settings_rows(h)) return rc;
+  for (int i = 0; i < h->B; ++i) merge_updatable(h->rows[i], rows[i]);
+  if (int rc = upload_settings(h)) return old.restore(rc);
+  return 0;
+}
+
+// osqp_update_rho: the setting and every instance's carried rho <- the clipped value(s); rho [B]
+// (host) or null: rho_all for every instance
+static int update_rho(mpcqp_handle* h, const double* rho, double rho_all) {
+  const size_t B = (size_t)h->B;
+  for (size_t i = 0; i < B; ++i)
+    if (!((rho ? rho[i] : rho_all) > 0))
+      return set_error(MPCQP_E_INVALID, (rho ? "row " + std::to_string(i) + ": " : std::string()) +
+                                            "rho must be positive");
+  SettingsBackup old(h);
+  if (rho)
+    if (int rc = settings_rows(h)) return rc;
+  h->set.rho = rho ? h->set.rho : clip_rho(rho_all);
+  for (size_t i = 0; i < h->rows.size(); ++i) h->rows[i].rho = clip_rho(rho ? rho[i] : rho_all);
+  if (int rc = upload_settings(h)) return old.restore(rc);
+  h->stage.resize(B * sizeof(double));
+  for (size_t i = 0; i < B; ++i) ((double*)h->stage.data())[i] = clip_rho(rho ? rho[i] : rho_all);
+  // (a carried rho half-written by a failed copy cannot be put back: the settings are)
+  if (int rc = upload(h, h->rho, B)) return old.restore(rc);
+  return 0;
+}
+
+int mpcqp_update_rho(mpcqp_handle* h, double rho) {
+  if (int rc = guard(h)) return rc;
+  return update_rho(h, nullptr, rho);
+}
+
+int mpcqp_update_rho_batched(mpcqp_handle* h, const double* rho) {
+  if (int rc = guard(h, rho)) return rc;
+  return update_rho(h, rho, 0.0);
+}
+
+int mpcqp_get_settings(const mpcqp_handle* h, mpcqp_settings* rows) {
+  if (int rc = guard(h, rows)) return rc;
+  for (int i = 0; i < h->B; ++i) rows[i] = h->rows.empty() ? h->set : h->rows[i];
+  return 0;
 }
 
 int mpcqp_update_bounds(mpcqp_handle* h, const double* l, const double* u) {
@@ -2779,7 +3041,8 @@ int mpcqp_solve(mpcqp_handle* h, double* x, double* y, const mpcqp_info* info) {
   const SetupRows s = setup_rows(h, h->batched);
   KParams p{};
   p.pl = h->dp;
-  p.s = h->set;
+  p.srows = h->rows.empty() ? h->d_set : h->d_rows;
+  p.sstride = h->rows.empty() ? 0 : (int)sizeof(mpcqp_settings);
   p.B = h->B;
   p.Px = s.Px, p.q = s.q, p.Px_stride = s.Px_stride, p.q_stride = s.q_stride;
   p.Ax = h->Ax, p.l = h->l, p.u = h->u;
@@ -2792,7 +3055,6 @@ int mpcqp_solve(mpcqp_handle* h, double* x, double* y, const mpcqp_info* info) {
   p.scratch = h->scratch;
   p.counter = h->counter;
   p.timing = h->timing;
-  p.rho0 = std::min(std::max(h->set.rho, RHO_MIN), RHO_MAX);
   p.skip = h->skip;
   p.order = h->order;
   HIPCHK(hipMemsetAsync(h->counter, 0, 64, h->stream));

@@ -160,7 +160,7 @@ using Resid2 = Resid<RNH, RMH>;
 // KKT (re)assembly and factorization by both waves (the elimination chain on wave 0)
 template <int RNH, int RMH>
 __device__ __forceinline__ void assemble_and_factor2(const KParams& p, double* v, const Wv& W,
-                                                     const Inst2<RNH, RMH>& S) {
+                                                     const Inst2<RNH, RMH>& S, double sigma) {
   const DevPlan& P = p.pl;
   const int tid = W.lane + 64 * W.w;
   for (int k = tid; k < P.nnzL; k += 128) v[P.LX + k] = 0.0;
@@ -171,11 +171,11 @@ __device__ __forceinline__ void assemble_and_factor2(const KParams& p, double* v
     v[P.MONE] = -1.0;
   }
   BAR2_X(v, p.pl.XID);
-  for (int j = tid; j < P.n; j += 128) v[P.slotSig[j]] = p.s.sigma;
+  for (int j = tid; j < P.n; j += 128) v[P.slotSig[j]] = sigma;
   BAR2_X(v, p.pl.XID);
   for (int k = tid; k < P.nnzP; k += 128) {
     const double val = v[P.MV + k];
-    v[P.slotP[k]] = (P.Pi[k] == P.Pcol[k]) ? val + p.s.sigma : val;
+    v[P.slotP[k]] = (P.Pi[k] == P.Pcol[k]) ? val + sigma : val;
   }
   for (int k = tid; k < P.nnzA; k += 128) v[P.slotA[k]] = v[P.MV + P.nnzP + k];
 #pragma unroll
@@ -251,7 +251,8 @@ __device__ __forceinline__ void scale_problem2(const KParams& p, int inst, const
   double cprev = 1.0;
   double dpc[RNH];
   BAR2_X(v, p.pl.XID);
-  for (int it = 0; it < p.s.scaling; ++it) {
+  const int scaling = uniform_i(set_row(p, inst)->scaling);
+  for (int it = 0; it < scaling; ++it) {
     double dp[RNH], da[RNH], er[RMH], dt[RNH], et[RMH];
     if (it == 0) {
       ell_absmax_r<false>(P.eP, iP, 0u, v, dp, W, W.xo);
@@ -408,15 +409,16 @@ __device__ __forceinline__ void solve_instance2(const KParams& p, int inst, doub
     }
   }
   T_END(T_SCALE, t_sc);
-  S.rho = (hs != 0) ? p.rho_state[inst] : p.rho0;
+  const SetRow sr = set_row(p, inst);  // the instance's own settings (KParams::srows)
+  S.rho = (hs != 0) ? p.rho_state[inst] : sr->rho;
   set_rho(S);
   T_BEGIN(t_f0);
-  assemble_and_factor2<RNH, RMH>(p, v, W, S);
+  assemble_and_factor2<RNH, RMH>(p, v, W, S, sr->sigma);
   T_END(T_FACTOR, t_f0);
   T_COUNT(T_NFACT);
 
   // ---------------- warm start (own slots)
-  const bool warm = p.s.warm_start && hs != 0;
+  const bool warm = uniform_i(sr->warm_start) && hs != 0;
   if (warm && hs == 1) {
 #pragma unroll
     for (int r = 0; r < RNH; ++r) {
@@ -495,12 +497,14 @@ __device__ __forceinline__ void solve_instance2(const KParams& p, int inst, doub
   auto and_d = [](double x, uint32_t mk) {
     return __hiloint2double((int)((uint32_t)__double2hiint(x) & mk), (int)((uint32_t)__double2loint(x) & mk));
   };
-  double sigma = p.s.sigma, alpha = p.s.alpha, alpha_c = 1.0 - p.s.alpha;
+  double sigma = sr->sigma, alpha = sr->alpha, alpha_c = 1.0 - sr->alpha;
   asm volatile("" : "+v"(sigma), "+v"(alpha), "+v"(alpha_c));
-  const int chk = p.s.check_termination;
-  int ar_int = p.s.adaptive_rho_interval;
-  if (p.s.adaptive_rho && ar_int == 0) ar_int = chk ? 4 * chk : 100;
-  if (!p.s.adaptive_rho) ar_int = 0;
+  // read once per instance, before the loop, through readfirstlane (the one-wave kernel's)
+  const int chk = uniform_i(sr->check_termination);
+  int ar_int = uniform_i(sr->adaptive_rho_interval);
+  const int ar_on = uniform_i(sr->adaptive_rho);
+  if (ar_on && ar_int == 0) ar_int = chk ? 4 * chk : 100;
+  if (!ar_on) ar_int = 0;
   int chk_left = chk, ar_left = ar_int;
   int status = MPCQP_UNSOLVED, iter = 0, rho_updates = 0;
   bool can_check = false;
@@ -529,7 +533,8 @@ __device__ __forceinline__ void solve_instance2(const KParams& p, int inst, doub
   };
   load_dinv();
   // the loop bounds as opaque SGPR values (the one-wave kernel's max_iter / chk_s / ar_s)
-  int max_iter = p.s.max_iter;
+  int max_iter = uniform_i(sr->max_iter);
+  const RowTol<false> tol{vector_id(inst)};  // the check blocks load the row where they use it
   int chk_s = chk, ar_s = ar_int;
   asm volatile("" : "+s"(max_iter), "+s"(chk_s), "+s"(ar_s));
   for (iter = 1; iter <= max_iter; ++iter) {
@@ -677,7 +682,7 @@ __device__ __forceinline__ void solve_instance2(const KParams& p, int inst, doub
       T_COUNT(T_NCHK);
     }
     if (can_check) {
-      status = check_termination(p, S, R, dy, dx, sb, v, C, false TACC_ARG);
+      status = check_termination(p, tol, S, R, dy, dx, sb, v, C, false TACC_ARG);
       if (status != 0) {
         W.ph = C.ph;  // the exchange buffer phase carries on
         break;
@@ -686,13 +691,13 @@ __device__ __forceinline__ void solve_instance2(const KParams& p, int inst, doub
     }
     if (adapt) {
       const double rho_new = rho_estimate(p, S, R, v, C);
-      if (rho_new > S.rho * p.s.adaptive_rho_tolerance ||
-          rho_new < S.rho / p.s.adaptive_rho_tolerance) {
+      const double ar_tol = tol_adaptive_rho(p, tol);
+      if (rho_new > S.rho * ar_tol || rho_new < S.rho / ar_tol) {
         S.rho = dmind(dmaxd(rho_new, RHO_MIN), RHO_MAX);
         set_rho(S);
         rho_updates++;
         T_BEGIN(t_f1);
-        assemble_and_factor2<RNH, RMH>(p, v, C, S);
+        assemble_and_factor2<RNH, RMH>(p, v, C, S, sigma);
         load_dinv();
 #ifdef MPCQP_TIMING
         const unsigned long long dt_f1 = __builtin_amdgcn_s_memtime() - t_f1;
@@ -710,12 +715,12 @@ __device__ __forceinline__ void solve_instance2(const KParams& p, int inst, doub
     iter = iter - 1;
     BAR2_X(v, p.pl.XID);
     compute_residuals(p, S, R, v, W TACC_ARG);
-    status = check_termination(p, S, R, dy, dx, sb, v, W, false TACC_ARG);
+    status = check_termination(p, tol, S, R, dy, dx, sb, v, W, false TACC_ARG);
     if (status == 0) status = MPCQP_UNSOLVED;
   }
-  if (iter > p.s.max_iter) iter = p.s.max_iter;
+  if (iter > max_iter) iter = max_iter;
   if (status == MPCQP_UNSOLVED) {
-    const int st = check_termination(p, S, R, dy, dx, sb, v, W, true TACC_ARG);
+    const int st = check_termination(p, tol, S, R, dy, dx, sb, v, W, true TACC_ARG);
     status = st ? st : MPCQP_MAX_ITER_REACHED;
   }
 

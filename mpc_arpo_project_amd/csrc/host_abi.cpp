@@ -32,6 +32,17 @@ int set_error(int code, const std::string& msg) {
   return code;
 }
 
+int check_settings_row(const mpcqp_settings& s, int row) {
+  const std::string at = row >= 0 ? "row " + std::to_string(row) + ": " : "";
+  if (s.polish) return set_error(MPCQP_E_UNSUPPORTED, at + "polish is not implemented in this build");
+  if (s.scaled_termination)
+    return set_error(MPCQP_E_UNSUPPORTED, at + "scaled_termination is not implemented in this build");
+  if (s.max_iter <= 0 || s.alpha <= 0 || s.alpha >= 2 || s.sigma <= 0 || s.rho <= 0 ||
+      s.scaling < 0 || s.check_termination < 0 || s.eps_abs < 0 || s.eps_rel < 0)
+    return set_error(MPCQP_E_INVALID, at + "invalid settings");
+  return 0;
+}
+
 // waves per instance of the solve kernel (MPCQP_WAVES: 1; 2 = two waves, solve steps split
 // between them; 3 = two waves, solve steps on the first; unset or 0: chosen per structure by
 // auto_waves; DESIGN.md, Two waves per instance)
@@ -231,7 +242,7 @@ using namespace mpcqp;
 
 extern "C" {
 
-int mpcqp_version(void) { return 101; }
+int mpcqp_version(void) { return 102; }
 const char* mpcqp_last_error(void) { return g_err.c_str(); }
 
 const char* mpcqp_status_string(int32_t st) {
@@ -271,6 +282,14 @@ int mpcqp_default_settings(mpcqp_settings* s) {
   s->check_termination = 25;
   s->warm_start = 1;
   s->scaled_termination = 0;
+  return 0;
+}
+
+int mpcqp_check_settings(const mpcqp_settings* rows, int32_t count) {
+  if (!rows) return set_error(MPCQP_E_INVALID, "null settings");
+  if (count <= 0) return set_error(MPCQP_E_INVALID, "invalid count");
+  for (int32_t i = 0; i < count; ++i)
+    if (int rc = check_settings_row(rows[i], i)) return rc;
   return 0;
 }
 

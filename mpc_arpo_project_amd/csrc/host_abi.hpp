@@ -15,4 +15,8 @@ int auto_waves(const mpcqp_structure* st);
 // the plan mpcqp_create builds for a structure (block caps, step kind, waves, layout); false with
 // pl.error set if the structure is unsupported
 bool plan_for(const mpcqp_structure* st, Plan& pl);
+// The validation of one settings struct (mpcqp_create's rules and messages): 0, or the error set
+// (MPCQP_E_UNSUPPORTED naming polish / scaled_termination, MPCQP_E_INVALID "invalid settings").
+// row >= 0: the message starts with "row <row>: " (the per-instance forms, mpcqp_check_settings)
+int check_settings_row(const mpcqp_settings& s, int row = -1);
 }  // namespace mpcqp

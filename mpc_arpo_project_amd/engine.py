@@ -71,7 +71,11 @@ class BatchQP:
         if self.A.shape[1] != self.n:
             raise ValueError("A must have n columns")
         self.B = int(batch)
-        self.settings = _lib.default_settings(**settings)
+        # any setting may be a length-B array: one value per instance (mpcqp_set_settings_batched,
+        # sent below before any data); the handle itself is created with the scalar ones
+        rows = _lib.settings_rows(self.B, **settings) if _lib.per_instance(settings) else None
+        self.settings = _lib.default_settings(
+            **{k: v for k, v in settings.items() if np.ndim(v) == 0})
         self._Pp = np.ascontiguousarray(self.P.indptr, dtype=np.int32)
         self._Pi = np.ascontiguousarray(self.P.indices, dtype=np.int32)
         self._Ap = np.ascontiguousarray(self.A.indptr, dtype=np.int32)
@@ -88,6 +92,9 @@ class BatchQP:
                                           C.c_void_p(self.stream.cuda_stream), C.byref(h)),
                   "mpcqp_create")
         self._h = h
+        if rows is not None:
+            check(_lib.lib().mpcqp_set_settings_batched(self._h, rows),
+                  "mpcqp_set_settings_batched")
         self.nnzP = int(self.P.nnz)
         self.nnzA = int(self.A.nnz)
         self._has_data = False
@@ -185,6 +192,56 @@ class BatchQP:
             check(_lib.lib().mpcqp_update_A(self._h, Ax.data_ptr()), "mpcqp_update_A")
             keep["Ax"] = Ax
         self._keep(**keep)
+
+    # set-up settings: fixed by the scaling and the factorization set-up, not updatable (OSQP's too)
+    SETUP_SETTINGS = ("sigma", "scaling", "adaptive_rho", "adaptive_rho_interval",
+                      "adaptive_rho_tolerance")
+
+    def _settings_rows(self):
+        rows = (_lib.Settings * self.B)()
+        check(_lib.lib().mpcqp_get_settings(self._h, rows), "mpcqp_get_settings")
+        return rows
+
+    def get_settings(self):
+        """The settings in force (mpcqp_get_settings): {name: array of B values}."""
+        view = _lib.rows_view(self._settings_rows())
+        return {name: view[name].copy() for name, _ in _lib.Settings._fields_}
+
+    def update_settings(self, **kw):
+        """OSQP's update_settings(): max_iter, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, alpha,
+        check_termination, warm_start (mpcqp_update_settings) and rho (osqp_update_rho:
+        mpcqp_update_rho), each a scalar or a length-B sequence, one value per instance.  Iterates,
+        carried rho (unless given) and data scaling are kept.  A set-up setting is a ValueError."""
+        kw = {_lib._setting_key(k): v for k, v in kw.items() if k != "verbose"}
+        for k in kw:
+            if k in self.SETUP_SETTINGS:
+                raise ValueError(f"'{k}' is a set-up setting: it cannot be updated after creation")
+        rho = kw.pop("rho", None)
+        if kw:
+            rows = self._settings_rows()
+            # rows that differ (however they were set) are updated row by row: the shared form
+            # would write row 0's updatable fields into every row
+            view = _lib.rows_view(rows)  # a numpy view: whole columns at once
+            mixed = any(bool((view[n] != view[n][0]).any()) for n, _ in _lib.Settings._fields_)
+            for k, v in kw.items():
+                view[k] = _lib.setting_column(self.B, k, v)
+            if mixed or _lib.per_instance(kw):
+                check(_lib.lib().mpcqp_update_settings_batched(self._h, rows),
+                      "mpcqp_update_settings_batched")
+            else:
+                check(_lib.lib().mpcqp_update_settings(self._h, C.byref(rows[0])),
+                      "mpcqp_update_settings")
+                for k in kw:
+                    setattr(self.settings, k, getattr(rows[0], k))
+        if rho is not None:
+            if np.ndim(rho) == 0:
+                check(_lib.lib().mpcqp_update_rho(self._h, float(rho)), "mpcqp_update_rho")
+            else:
+                r = np.ascontiguousarray(rho, dtype=np.float64).reshape(-1)
+                if r.size != self.B:
+                    raise ValueError(f"setting 'rho' has {r.size} values for a batch of {self.B}")
+                check(_lib.lib().mpcqp_update_rho_batched(
+                    self._h, r.ctypes.data_as(C.POINTER(C.c_double))), "mpcqp_update_rho_batched")
 
     def _on_stream(self, fn, *tensors):
         """run fn (an ABI call that queues copies on the handle's stream) into freshly allocated

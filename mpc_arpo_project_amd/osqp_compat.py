@@ -21,7 +21,7 @@ from types import SimpleNamespace
 import numpy as np
 import scipy.sparse as sp
 
-from ._lib import STATUS
+from ._lib import STATUS, MPCQPError
 from .engine import BatchQP, sorted_csc, triu_csc
 
 OSQP_INFTY = 1e30
@@ -105,6 +105,35 @@ class OSQP:
                 raise ValueError("Ax must have nnz(A) entries")
             self._A.data[:] = Ax
             self._qp.update(Ax=Ax)
+
+    def update_settings(self, **kw):
+        """osqp's update_settings(): max_iter, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, rho,
+        alpha, delta, polish_refine_iter, check_termination, warm_start (osqp_update_<setting>).
+        verbose is ignored; time_limit other than 0, polish and scaled_termination are refused as
+        setup refuses them; any other key is a ValueError."""
+        if self._qp is None:
+            raise ValueError("setup must be called first")
+        allowed = ("max_iter", "eps_abs", "eps_rel", "eps_prim_inf", "eps_dual_inf", "rho", "alpha",
+                   "delta", "polish_refine_iter", "check_termination", "warm_start", "warm_starting")
+        send = {}
+        for k, v in kw.items():
+            if k == "verbose":
+                continue
+            if k == "time_limit":
+                if v:
+                    raise ValueError("time_limit is not implemented in this build")
+                continue
+            if k in ("polish", "scaled_termination"):
+                if v:  # the error mpcqp_create gives setup
+                    raise MPCQPError(f"{k} is not implemented in this build")
+                continue
+            if k not in allowed:
+                raise ValueError(f"unknown or non-updatable setting '{k}'")
+            if np.ndim(v) != 0:
+                raise ValueError(f"setting '{k}' must be a scalar")
+            send[k] = v
+        if send:
+            self._qp.update_settings(**send)
 
     def warm_start(self, x=None, y=None):
         if x is None or y is None:

@@ -47,6 +47,14 @@ and noise realisations (common random numbers).  Ranks and shards stay contiguou
 hold several weight sets, in one batch (per-instance P and q, mpcqp_set_data_batched).  The summary
 keeps its [G, 9] layout; the JSON line gains "variants": the headline statistics per weight set.
 
+Solver-setting variants: `--max-iter 25,100,4000 --eps-list 1e-2,1e-3` runs every scenario once per
+solver set, the product of the lists (eps sets eps_abs = eps_rel), under the same initial
+conditions and noise; `Sweep(solver_sets=[dict(...), ...])` takes any per-instance setting
+(mpcqp_set_settings_batched).  Each step selects the controller from the solve's status, so the
+iteration budget and the tolerances are controller-tuning knobs: success rate and fallback share
+per set come out of one batch.  With W weight sets and S solver sets the variant of global id g is
+v = g // G0 = w * S + s (`solver_variant_index`); "variants" lists them in that order.
+
   --noise-stream reference (default): the reference's own noise.  trajectorySimulate re-seeds
         numpy's global generator with 123 at every call (src/trajectorySimulate.py:28) and draws
         noiseVec = sigMat @ normal(0, 1, 4) from it (:268, :352-356), so every Monte-Carlo run of
@@ -142,44 +150,81 @@ def variant_index(lo: int, hi: int, G0: int, n_ics: int):
     return g // G0, g0, g0 % n_ics, g0
 
 
+def solver_variant_index(lo: int, hi: int, G0: int, n_ics: int, S: int = 1):
+    """global ids [lo, hi) of a sweep with weight sets x S solver sets -> (w, s, g0, ic, key)
+    arrays: g = v * G0 + g0 with v = w * S + s runs weight set w and solver set s on initial
+    condition ic under noise stream key (variant_index)"""
+    v, g0, ic, key = variant_index(lo, hi, G0, n_ics)
+    return v // S, v % S, g0, ic, key
+
+
+def solver_set_arrays(solver_sets, s, base):
+    """per-instance settings of instances running solver sets s (int array): for every key that
+    any set names, the set's value, else base's, else the engine default -> {key: array}"""
+    from . import _lib
+
+    dflt = _lib.default_settings()
+    out = {}
+    for k in sorted({k for st in solver_sets for k in st}):
+        key = _lib._setting_key(k)
+        vals = np.array([st.get(k, base.get(key, getattr(dflt, key))) for st in solver_sets])
+        out[key] = vals[s]
+    return out
+
+
 class Sweep:
     """The rank-local part of a sweep (device closed loops + run summaries)."""
 
     def __init__(self, scenario="radial", n_seeds=1, n_ics=1024, Nx=40, noise=(0.75, 0.75, 50),
                  isReject=True, T_final=150.0, rank=0, world=1, device="cuda", shards=2,
                  ic_seed=20250328, noise_seed=123, eps=1e-3, keep_traj=False, x0=None,
-                 noise_source=None, variants=None, weights=None):
+                 noise_source=None, variants=None, weights=None, solver=None, solver_sets=None):
         """variants: a list of (q_scale, r_scale, rs_scale) weight sets, every scenario once per
-        set (module docstring); weights: one such triple for a plain sweep (shared cost data)"""
+        set (module docstring); weights: one such triple for a plain sweep (shared cost data).
+        solver_sets: a list of dicts of solver settings, every scenario once per set (and per
+        weight set: v = w * S + s); solver: one such dict for a plain sweep (shared settings)"""
         import torch
 
         from .closed_loop import ShardedClosedLoop
 
         self.G0 = n_seeds * n_ics
-        self.V = 1 if variants is None else len(variants)
-        if self.V < 1:
+        self.W = 1 if variants is None else len(variants)
+        self.S = 1 if solver_sets is None else len(solver_sets)
+        if self.W < 1:
             raise ValueError("variants must name at least one weight set")
+        if self.S < 1:
+            raise ValueError("solver_sets must name at least one set of settings")
+        if solver is not None and solver_sets is not None:
+            raise ValueError("give the solver settings either as solver_sets or as one solver dict")
+        self.V = self.W * self.S
         self.G = self.V * self.G0
         self.lo, self.hi = launch.shard_range(self.G, rank, world)
         kw = {}
         if variants is not None and weights is not None:
             raise ValueError("give the weight sets either as variants or as one weights triple")
-        if variants is None:
+        # the reference's default OSQP tolerances (eps_abs = eps_rel = 1e-3) unless asked otherwise
+        settings = dict(eps_abs=eps, eps_rel=eps, **(solver or {}))
+        if variants is None and solver_sets is None:
             self.sim, self.prob = build(scenario, Nx, noise, isReject, T_final, weights)
             X = scenario_states(scenario, n_seeds, n_ics, self.lo, self.hi, ic_seed, x0)
         else:
             if noise_source is not None:
                 raise ValueError("a host noise source draws per batch row: not with variants")
-            built = [build(scenario, Nx, noise, isReject, T_final, w) for w in variants]
-            self.sim, self.prob = built[0][0], [b[1] for b in built]
-            v, g0, _, _ = variant_index(self.lo, self.hi, self.G0, n_ics)
+            w, s, g0, _, _ = solver_variant_index(self.lo, self.hi, self.G0, n_ics, self.S)
             X = scenario_states(scenario, n_seeds, n_ics, 0, self.G0, ic_seed, x0)[g0]
-            kw = dict(variant=v, id_period=self.G0)
+            kw = dict(id_period=self.G0)
+            if variants is None:
+                self.sim, self.prob = build(scenario, Nx, noise, isReject, T_final, weights)
+            else:
+                built = [build(scenario, Nx, noise, isReject, T_final, wt) for wt in variants]
+                self.sim, self.prob = built[0][0], [b[1] for b in built]
+                kw["variant"] = w
+            if solver_sets is not None:
+                settings.update(solver_set_arrays(solver_sets, s, settings))
         self.nsim = int(self.sim.T_final / self.sim.time_stp)
-        # the reference's default OSQP tolerances (eps_abs = eps_rel = 1e-3) unless asked otherwise
         self.loop = ShardedClosedLoop(self.prob, X, shards=shards, device=device, id_offset=self.lo,
-                                      noise=noise, noise_seed=noise_seed, eps_abs=eps, eps_rel=eps,
-                                      noise_source=noise_source, **kw)
+                                      noise=noise, noise_seed=noise_seed,
+                                      noise_source=noise_source, **settings, **kw)
         self.loop.enable_tracking(self.nsim, *self.sim.suc_cond)
         self.traj = None
         if keep_traj:
@@ -363,7 +408,21 @@ def main(argv=None):
         ap.add_argument(flag, default=None,
                         help=f"comma list of multipliers of the scenario's {what}; the weight sets "
                              "of the sweep are the product of the three lists (module docstring)")
+    ap.add_argument("--max-iter", default=None,
+                    help="comma list of ADMM iteration budgets; with --eps-list the solver sets of "
+                         "the sweep are the product of the two lists (module docstring)")
+    ap.add_argument("--eps-list", default=None,
+                    help="comma list of tolerances (eps_abs = eps_rel) of the solver sets")
     a = ap.parse_args(argv[1:])
+    solver_sets = None
+    if a.max_iter or a.eps_list:
+        if a.experiment:
+            ap.error("--max-iter / --eps-list do not combine with --experiment")
+        its = [int(x) for x in a.max_iter.split(",")] if a.max_iter else [None]
+        eps = [float(x) for x in a.eps_list.split(",")] if a.eps_list else [None]
+        solver_sets = [dict(([("max_iter", mi)] if mi is not None else []) +
+                            ([("eps_abs", e), ("eps_rel", e)] if e is not None else []))
+                       for mi in its for e in eps]
     variants = None
     if a.q_scale or a.r_scale or a.rs_scale:
         if a.experiment:
@@ -396,7 +455,7 @@ def main(argv=None):
         noise = (noise[0], noise[1], int(noise[2]))
     sw = Sweep(a.scenario, a.seeds, a.ics, Nx=a.nx, noise=noise, isReject=not a.no_reject,
                T_final=a.tfinal, rank=rank, world=world, device=device, shards=a.shards,
-               eps=a.eps, keep_traj=a.traj, variants=variants)
+               eps=a.eps, keep_traj=a.traj, variants=variants, solver_sets=solver_sets)
     el = _timed_run(sw, dist, device)
     local_sum = sw.summary()
     S = launch.gather_rows(local_sum, sw.G, rank, world, dist)
@@ -412,9 +471,19 @@ def main(argv=None):
         out.update(scenario=a.scenario, n_gpus=world, seeds=a.seeds, ics=a.ics, nx=a.nx,
                    noise=a.noise, reject=not a.no_reject, steps=sw.steps, seconds=el,
                    scenarios_per_s=sw.G / el, solves_per_s=solved_steps / el)
-        if variants is not None:
-            out["variants"] = [dict(q_scale=w[0], r_scale=w[1], rs_scale=w[2], **r)
-                               for w, r in zip(variants, reduce_variants(Sn, len(variants)))]
+        if variants is not None or solver_sets is not None:
+            # v = w * S + s; an entry names its weight set and the solver fields that differ
+            nS = sw.S
+            differ = [k for k in sorted({k for st in solver_sets or [] for k in st})
+                      if len({st.get(k) for st in solver_sets}) > 1]
+            out["variants"] = []
+            for v, r in enumerate(reduce_variants(Sn, sw.V)):
+                e = {}
+                if variants is not None:
+                    wt = variants[v // nS]
+                    e.update(q_scale=wt[0], r_scale=wt[1], rs_scale=wt[2])
+                e.update({k: solver_sets[v % nS][k] for k in differ})
+                out["variants"].append(dict(**e, **r))
         if a.out:
             np.save(a.out, Sn)
             if traj is not None:
