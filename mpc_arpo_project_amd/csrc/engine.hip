@@ -94,15 +94,38 @@ struct KParams {
   const int32_t* order;  // [B] or null: the k-th instance handed out is order[k] (mpcqp_set_order)
 };
 
+// the set-up row of instance inst (KParams::Px / q with their stride; 0: the shared row).
+// Wave-uniform: scalar address arithmetic, the product in 64 bits
+__device__ __forceinline__ const double* setup_row(const double* base, int stride, int inst) {
+  return base + (size_t)inst * (size_t)stride;
+}
+// the drift buffers' rows of instance inst: P values (cnt = nnzP, base p.Pw) or q (n, p.qw)
+__device__ __forceinline__ double* drift_row(double* base, int b, int B, int cnt, int inst) {
+  return base + ((size_t)b * B + inst) * cnt;
+}
 // Where a solve's Ruiz passes start and where the data they leave for the next solve goes (OSQP
-// 0.6's data drift, KParams::Pw).  Wave-uniform.  drift_sel: the buffer indices; drift_of: the
-// pointers formed from them at the solve's start (one-wave kernel).  The two-wave kernel forms the
-// pointers at their two uses instead: measured per kernel, each form is 1.5-1.9 % faster in its own
-// kernel (register allocation).
+// 0.6's data drift, KParams::Pw).  Wave-uniform.  drift_sel is the one state machine: the buffer
+// indices, the bounds rule and dsel after the solve.  The kernels differ only in where they turn the
+// indices into pointers: the one-wave kernel at the solve's start (drift_of -> Drift), the two-wave
+// kernel at their uses (DriftSel's own accessors); measured per kernel, each form is 1.5-1.9 %
+// faster in its own kernel (register allocation; DESIGN.md, Codegen sensitivity).  scale_problem
+// reads either through in_P / in_q / out_P / out_q.
 struct DriftSel {
   int in_b, out_b;  // drift buffer the Ruiz passes scale (-1: the set-up data) / unscale into
   bool rebound;     // bounds through E_old, E_old^-1, E_new (osqp_update_A after update_bounds)
   int sel;          // dsel after this solve
+  __device__ __forceinline__ const double* in_P(const KParams& p, int inst) const {
+    return in_b < 0 ? setup_row(p.Px, p.Px_stride, inst) : drift_row(p.Pw, in_b, p.B, p.pl.nnzP, inst);
+  }
+  __device__ __forceinline__ const double* in_q(const KParams& p, int inst) const {
+    return in_b < 0 ? setup_row(p.q, p.q_stride, inst) : drift_row(p.qw, in_b, p.B, p.pl.n, inst);
+  }
+  __device__ __forceinline__ double* out_P(const KParams& p, int inst) const {
+    return drift_row(p.Pw, out_b, p.B, p.pl.nnzP, inst);
+  }
+  __device__ __forceinline__ double* out_q(const KParams& p, int inst) const {
+    return drift_row(p.qw, out_b, p.B, p.pl.n, inst);
+  }
 };
 __device__ __forceinline__ DriftSel drift_sel(const KParams& p, int inst) {
   const int sel = __builtin_amdgcn_readfirstlane(p.dsel[inst]);
@@ -117,11 +140,6 @@ __device__ __forceinline__ DriftSel drift_sel(const KParams& p, int inst) {
     d.in_b = sel, d.out_b = sel == 0 ? 1 : 0, d.rebound = false, d.sel = sel;
   }
   return d;
-}
-// the set-up row of instance inst (KParams::Px / q with their stride; 0: the shared row).
-// Wave-uniform: scalar address arithmetic, the product in 64 bits
-__device__ __forceinline__ const double* setup_row(const double* base, int stride, int inst) {
-  return base + (size_t)inst * (size_t)stride;
 }
 // the settings row of instance inst (KParams::srows with its stride; 0: the shared row), in the
 // constant address space: its fields are read with scalar loads, as the kernel arguments are (the
@@ -151,30 +169,22 @@ __device__ __forceinline__ const mpcqp_settings* set_row_at_use(const KParams& p
   asm volatile("" : "+v"(vinst));
   return (const mpcqp_settings*)((const char*)p.srows + (size_t)(vinst * (uint32_t)p.sstride));
 }
-// the drift buffers' rows of instance inst: P values (cnt = nnzP, base p.Pw) or q (n, p.qw)
-__device__ __forceinline__ double* drift_row(double* base, int b, int B, int cnt, int inst) {
-  return base + ((size_t)b * B + inst) * cnt;
-}
 struct Drift {
   const double *P_in, *q_in;  // the unscaled P values / q the Ruiz passes scale
   double *P_out, *q_out;      // unscale_data of this solve's scaled P / q
   bool rebound;               // bounds through E_old, E_old^-1, E_new (osqp_update_A after update_bounds)
   int sel;                    // dsel after this solve
+  __device__ __forceinline__ const double* in_P(const KParams&, int) const { return P_in; }
+  __device__ __forceinline__ const double* in_q(const KParams&, int) const { return q_in; }
+  __device__ __forceinline__ double* out_P(const KParams&, int) const { return P_out; }
+  __device__ __forceinline__ double* out_q(const KParams&, int) const { return q_out; }
 };
 __device__ __forceinline__ Drift drift_of(const KParams& p, int inst) {
   const int nP = p.pl.nnzP, n = p.pl.n;
-  const int sel = __builtin_amdgcn_readfirstlane(p.dsel[inst]);
-  const bool dirty = p.a_inplace != 0 || __builtin_amdgcn_readfirstlane(p.pend[inst]) != 0;
-  int in_b, out_b;  // -1: the set-up data
+  const DriftSel s = drift_sel(p, inst);
+  const int in_b = s.in_b, out_b = s.out_b;
   Drift d;
-  if (sel == -2) {  // first solve after set_data: scale_data of the set-up data (osqp_setup)
-    in_b = -1, out_b = 0, d.rebound = false, d.sel = -1;
-  } else if (dirty) {  // osqp_update_A: unscale_data of the last scaling, then scale_data
-    const int ub = sel == 0 ? 1 : 0;
-    in_b = ub, out_b = 1 - ub, d.rebound = true, d.sel = ub;
-  } else {  // bounds only: the last scaling again (same input, same D, E, c)
-    in_b = sel, out_b = sel == 0 ? 1 : 0, d.rebound = false, d.sel = sel;
-  }
+  d.rebound = s.rebound, d.sel = s.sel;
   const size_t BP = (size_t)p.B * nP, Bq = (size_t)p.B * n;
   d.P_in = in_b < 0 ? setup_row(p.Px, p.Px_stride, inst) : p.Pw + in_b * BP + (size_t)inst * nP;
   d.q_in = in_b < 0 ? setup_row(p.q, p.q_stride, inst) : p.qw + in_b * Bq + (size_t)inst * n;
@@ -193,12 +203,17 @@ __device__ __forceinline__ Drift drift_of(const KParams& p, int inst) {
 enum { T_SCALE, T_FACTOR, T_FWD, T_BWD, T_VEC, T_CHECK, T_TAIL, T_ITERS, T_NFACT, T_RESID, T_TERM, T_NCHK, T_ADAPT, T_SCFIN, T_V0, T_V1, T_V2, T_RS0, T_RS1, T_RS2, T_RS3, T_RS4, T_TM0, T_TM1, T_TM2, T_SC0, T_SC1, T_SC2, T_SC3, T_SCC, T_NSLOT };
 #ifdef MPCQP_TIMING
 #define T_BEGIN(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
+// a stamp only the kernels with `on` take (scale_problem: the one-wave kernel's)
+#define T_BEGIN_IF(on, v)     \
+  unsigned long long v = 0;   \
+  if constexpr (on) v = __builtin_amdgcn_s_memtime()
 #define T_END(slot, v) tacc[slot] += __builtin_amdgcn_s_memtime() - (v)
 #define T_COUNT(slot) tacc[slot] += 1
 // value dependency barrier: the timestamp after it waits for x
 #define TSYNC(x) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::"v"(x))
 #else
 #define T_BEGIN(v)
+#define T_BEGIN_IF(on, v)
 #define T_END(slot, v)
 #define T_COUNT(slot)
 #define TSYNC(x)
@@ -861,11 +876,12 @@ __device__ __forceinline__ Slab slab_of(const DevPlan& P, double* scr) {
   s.MV = scr + ((P.n + P.m + 1) & ~1);  // 16-byte aligned (the slab base is)
   return s;
 }
-// ---- wave contexts.  The check path (residual mat-vecs and norms, residuals, termination,
-// certificates, rho estimate, bounds, solution store) is written once, over the context C of the
-// wave that runs it: One for the one-wave kernel, Wv for each wave of the two-wave kernel
+// ---- wave contexts.  The Ruiz passes with the bounds and the MV copy (scale_problem,
+// scale_finish) and the check path (residual mat-vecs and norms, residuals,
+// termination, certificates, rho estimate, solution store) are written once, over the context C of
+// the wave that runs them: One for the one-wave kernel, Wv for each wave of the two-wave kernel
 // (engine_pair.inc).  A context gives
-//   lane, xo, zo   the wave's lane and its first n- / m-vector slot: slot r holds element
+//   w, lane, xo, zo  the wave, its lane and its first n- / m-vector slot: slot r holds element
 //                  lane + 64 (r + xo) (resp. zo); WAVES / THREADS per instance, tid(), first()
 //   all<K>()       all-reduce of K wave-uniform values over the instance's waves
 //   sync()         this phase's LDS traffic ordered before the next phase's, in every wave
@@ -923,7 +939,7 @@ __device__ int g_pair_inject = 0;
 // The one wave of the one-wave kernel.  mvb: the LDS image, or the wave's slab under KM_MVG
 struct One {
   static constexpr int WAVES = 1, THREADS = 64;
-  static constexpr int xo = 0, zo = 0;
+  static constexpr int w = 0, xo = 0, zo = 0;
   int lane;
   const double* mvb;
   template <int K>
@@ -1224,50 +1240,51 @@ __device__ __forceinline__ void ell_absmax_r(const EllDev& e, const EllIdx<R, KM
 //   v[S_P + k] = ((v[S_P + k] * f) * v[ra[k]]) * v[ca[k]],  f = cp for P's values, 1 for A's
 // -- scaling.c's mat_premult_diag / mat_postmult_diag, with the previous pass's cost factor c
 // (mat_mult_scalar on P) deferred into this pass: the same multiplications in the same order, and
-// x * 1.0 is exact.  The row / column scaling slots come from registers (JW pairs of u16 per
-// lane: value k = 64 j + lane, j < 2 JW).
+// x * 1.0 is exact.  The row / column scaling slots come from registers: the wave's value slots
+// are [j0, j0 + 2 JW) (value k = 64 j + lane of slot j; j0 = 0 in the one-wave kernel), JW pairs
+// of u16 per lane, pair jl / 2 for slot j0 + jl.
 template <int JW>
 __device__ __forceinline__ void scale_pa_r(double* v, int S_P, int nnzP, int cnt,
                                            const uint32_t (&ra)[JW], const uint32_t (&ca)[JW],
-                                           double cp, int lane) {
+                                           double cp, int lane, int j0) {
   constexpr int U = 8;  // values in flight per lane: all value reads of a batch, then its stores
   static_assert((2 * JW) % U == 0, "batches of U values");
 #pragma unroll
-  for (int j0 = 0; j0 < 2 * JW; j0 += U) {
-    if (64 * j0 >= cnt) break;  // wave-uniform
+  for (int jb = 0; jb < 2 * JW; jb += U) {
+    if (64 * (j0 + jb) >= cnt) break;  // wave-uniform
     double x[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const int j = j0 + u, k = 64 * j + lane, kc = k < cnt ? k : 0;
+      const int jl = jb + u, k = 64 * (j0 + jl) + lane, kc = k < cnt ? k : 0;
       const double f = k < nnzP ? cp : 1.0;
-      const uint32_t a = (j & 1) ? (ra[j / 2] >> 16) : (ra[j / 2] & 0xffffu);
-      const uint32_t b = (j & 1) ? (ca[j / 2] >> 16) : (ca[j / 2] & 0xffffu);
+      const uint32_t a = (jl & 1) ? (ra[jl / 2] >> 16) : (ra[jl / 2] & 0xffffu);
+      const uint32_t b = (jl & 1) ? (ca[jl / 2] >> 16) : (ca[jl / 2] & 0xffffu);
       x[u] = ((v[S_P + kc] * f) * v[a]) * v[b];
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const int k = 64 * (j0 + u) + lane;
+      const int k = 64 * (j0 + jb + u) + lane;
       if (k < cnt) v[S_P + k] = x[u];
     }
   }
 }
 // the inverse of the scaled P values for the next solve (unscale_data: mat_mult_scalar(P, c^-1),
 // mat_premult_diag / mat_postmult_diag(P, D^-1)): out[k] = ((v[S_P + k] c^-1) v[ra_k]) v[ca_k],
-// k < nnzP, the D_temp slots holding D^-1 -- the operand layout of scale_pa_r
+// k < nnzP, the D_temp slots holding D^-1 -- the operand layout and slot range of scale_pa_r
 template <int JW>
 __device__ __forceinline__ void unscale_p_r(const double* v, int S_P, int nnzP, const uint32_t (&ra)[JW],
-                                            const uint32_t (&ca)[JW], double cinv, int lane,
+                                            const uint32_t (&ca)[JW], double cinv, int lane, int j0,
                                             double* out) {
 #pragma unroll
-  for (int j = 0; j < 2 * JW; ++j) {
-    if (64 * j >= nnzP) break;  // wave-uniform
-    const int k = 64 * j + lane;
-    const uint32_t a = (j & 1) ? (ra[j / 2] >> 16) : (ra[j / 2] & 0xffffu);
-    const uint32_t b = (j & 1) ? (ca[j / 2] >> 16) : (ca[j / 2] & 0xffffu);
+  for (int jl = 0; jl < 2 * JW; ++jl) {
+    if (64 * (j0 + jl) >= nnzP) break;  // wave-uniform
+    const int k = 64 * (j0 + jl) + lane;
+    const uint32_t a = (jl & 1) ? (ra[jl / 2] >> 16) : (ra[jl / 2] & 0xffffu);
+    const uint32_t b = (jl & 1) ? (ca[jl / 2] >> 16) : (ca[jl / 2] & 0xffffu);
     if (k < nnzP) out[k] = ((v[S_P + k] * cinv) * v[a]) * v[b];
   }
 }
-// v[base + k] = src[k] for k < cnt, 8 loads per lane in flight
+// v[base + k] = src[k] for k < cnt, 8 loads per lane in flight (the one-wave kernel's value copies)
 __device__ __forceinline__ void load_vals(double* v, int base, const double* src, int cnt,
                                           int lane) {
   constexpr int U = 8;
@@ -1684,17 +1701,22 @@ __device__ __forceinline__ bool has_solution(int st) {
 // pass is LDS traffic only.  The column / row norms use the padded ELL lists (max is order-free);
 // padding entries read the zero slot S_ZERO, so no LDS read is conditional.  Returns D and E;
 // q, l, u (scaled) and c are left in S.
-template <int RN, int RM>
-__device__ __forceinline__ void scale_problem(const KParams& p, int inst, const Drift& dr, Inst<RN, RM>& S,
-                                              double* v, int lane, double (&D)[RN],
+// Written over the wave context: RN / RM are the wave's own n- / m-slots (all of them in the
+// one-wave kernel, half in the two-wave kernel), every elementwise pass, norm and factor is
+// computed by the owner of its element, the value overlay is rescaled by value slots (the wave's
+// are [w 2 JW, (w + 1) 2 JW)), and the syncs order one phase's LDS traffic before the next in every
+// wave.  dr: Drift (pointers formed at the solve's start) or DriftSel (formed here, at their uses).
+template <class Cx, class Dr, int RN, int RM>
+__device__ __forceinline__ void scale_problem(const KParams& p, int inst, const Dr& dr, Inst<RN, RM>& S,
+                                              double* v, Cx& C, double (&D)[RN],
                                               double (&E)[RM] TACC_PARAM) {
   const DevPlan& P = p.pl;
-  const int n = P.n, m = P.m;
-  // P and q: the set-up data, or the unscaled values OSQP holds (drift_of)
-  double* const Pw = dr.P_out;
-  double* const qw = dr.q_out;
-  const double* P_in = dr.P_in;
-  const double* q_in = dr.q_in;
+  const int n = P.n, m = P.m, lane = C.lane, tid = C.tid();
+  // seam: the phase stamps of the timing build are the one-wave kernel's
+  constexpr bool STAMPS = Cx::WAVES == 1;
+  // P and q: the set-up data, or the unscaled values OSQP holds (drift_sel)
+  const double* P_in = dr.in_P(p, inst);
+  const double* q_in = dr.in_q(p, inst);
   const double* Ax_in = p.Ax + (size_t)inst * P.nnzA;
   const double* l_in = p.l + (size_t)inst * m;
   const double* u_in = p.u + (size_t)inst * m;
@@ -1702,39 +1724,47 @@ __device__ __forceinline__ void scale_problem(const KParams& p, int inst, const 
   EllIdx<RN, ELL_KP> iP;
   EllIdx<RN, ELL_KAT> iAt;
   EllIdx<RM, ELL_KA> iA;
-  const One C{lane, v};
-  load_idx(P.eP, iP, lane, 0);
-  load_idx(P.eAt, iAt, lane, 0);
-  load_idx(P.eA, iA, lane, 0);
-  constexpr bool KF = RN == 2;
+  load_idx(P.eP, iP, lane, C.xo);
+  load_idx(P.eAt, iAt, lane, C.xo);
+  load_idx(P.eA, iA, lane, C.zo);
+  // seam: the used-slot flags are the (2, 4) one-wave kernel's (ell_absmax_r)
+  constexpr bool KF = Cx::WAVES == 1 && RN == 2;
   const uint32_t kfP = KF ? ell_kflags<RN>(P.eP) : 0u, kfAt = KF ? ell_kflags<RN>(P.eAt) : 0u,
                  kfA = KF ? ell_kflags<RM>(P.eA) : 0u;
-  constexpr int JW = 4 * RN;  // u16 pairs of row / column slots per lane (Plan::SJ <= 2 JW)
+  // u16 pairs of row / column slots per lane: the wave's value slots [j0, j0 + 2 JW) of the
+  // overlay's rescale operands (Plan::SJ <= 2 JW WAVES)
+  constexpr int JW = 4 * RN;
+  const int j0 = C.w * 2 * JW;
   uint32_t ra[JW], ca[JW];
   {
-    const uint2* rr = reinterpret_cast<const uint2*>(P.sra + (size_t)lane * P.SJ);
-    const uint2* cc = reinterpret_cast<const uint2*>(P.sca + (size_t)lane * P.SJ);
 #pragma unroll
     for (int q = 0; q < JW / 2; ++q) {
       ra[2 * q] = ra[2 * q + 1] = ca[2 * q] = ca[2 * q + 1] = 0u;
-      if (4 * q < P.SJ) {  // wave-uniform
-        const uint2 a = rr[q], c = cc[q];
+      const int jg = j0 + 4 * q;  // four u16 slots per 8-byte load
+      if (jg < P.SJ) {            // wave-uniform
+        const uint2 a = *reinterpret_cast<const uint2*>(P.sra + (size_t)lane * P.SJ + jg);
+        const uint2 c = *reinterpret_cast<const uint2*>(P.sca + (size_t)lane * P.SJ + jg);
         ra[2 * q] = a.x, ra[2 * q + 1] = a.y, ca[2 * q] = c.x, ca[2 * q + 1] = c.y;
       }
     }
   }
-  if (lane == 0) v[P.S_ZERO] = 0.0;
-  load_vals(v, P.S_P, P_in, P.nnzP, lane);
-  load_vals(v, P.S_A, Ax_in, P.nnzA, lane);
+  if (tid == 0) v[P.S_ZERO] = 0.0;
+  if constexpr (Cx::WAVES == 1) {  // seam: 8 loads in flight per lane / a strided loop
+    load_vals(v, P.S_P, P_in, P.nnzP, lane);
+    load_vals(v, P.S_A, Ax_in, P.nnzA, lane);
+  } else {
+    const int cnt = P.nnzP + P.nnzA;
+    for (int k = tid; k < cnt; k += Cx::THREADS) v[P.S_P + k] = k < P.nnzP ? P_in[k] : Ax_in[k - P.nnzP];
+  }
 #pragma unroll
   for (int r = 0; r < RN; ++r) {
-    const int j = lane + 64 * r;
+    const int j = lane + 64 * (r + C.xo);
     S.q[r] = j < n ? q_in[j] : 0.0;
     D[r] = 1.0;
   }
 #pragma unroll
   for (int r = 0; r < RM; ++r) {
-    const int i = lane + 64 * r;
+    const int i = lane + 64 * (r + C.zo);
     S.l[r] = i < m ? dmaxd(l_in[i], -OSQP_INFTY) : 0.0;
     S.u[r] = i < m ? dmind(u_in[i], OSQP_INFTY) : 0.0;
     E[r] = 1.0;
@@ -1742,12 +1772,12 @@ __device__ __forceinline__ void scale_problem(const KParams& p, int inst, const 
   S.c = 1.0;
   double cprev = 1.0;  // cost factor of the last pass, not yet applied to P's values
   double dpc[RN];      // P's column norms before that factor (the cost normalisation's)
-  LDS_FENCE();
+  C.sync(p, v);
   const int scaling = uniform_i(set_row(p, inst)->scaling);
   for (int it = 0; it < scaling; ++it) {
-    // (4, 8) bucket: the passes' operand addresses recomputed in every pass (hoisted out of the
-    // pass loop they held ~190 registers: that kernel's register peak, MPCQP_MAX_KERNEL_REGS)
-    if constexpr (RN >= 4) {
+    // seam, (4, 8) bucket: the passes' operand addresses recomputed in every pass (hoisted out of
+    // the pass loop they held ~190 registers: that kernel's register peak, MPCQP_MAX_KERNEL_REGS)
+    if constexpr (Cx::WAVES == 1 && RN >= 4) {
       opaque_idx(iP), opaque_idx(iAt), opaque_idx(iA);
       opaque_words(ra), opaque_words(ca);
     }
@@ -1756,37 +1786,41 @@ __device__ __forceinline__ void scale_problem(const KParams& p, int inst, const 
     // c (still pending on P's values): max_k |c x_k| = c max_k |x_k| exactly, rounding being
     // monotonic (c > 0)
     double dp[RN], da[RN], er[RM], dt[RN], et[RM];
-    T_BEGIN(t_s0);
+    T_BEGIN_IF(STAMPS, t_s0);
     if (it == 0) {
-      ell_absmax_r<KF>(P.eP, iP, kfP, v, dp, C, 0);
+      ell_absmax_r<KF>(P.eP, iP, kfP, v, dp, C, C.xo);
     } else {
 #pragma unroll
       for (int r = 0; r < RN; ++r) dp[r] = cprev * dpc[r];
     }
-    ell_absmax_r<KF>(P.eAt, iAt, kfAt, v, da, C, 0);
-    ell_absmax_r<KF>(P.eA, iA, kfA, v, er, C, 0);
-    TSYNC(er[RM - 1]);
-    T_END(T_SC0, t_s0);
-    T_BEGIN(t_s1);
+    ell_absmax_r<KF>(P.eAt, iAt, kfAt, v, da, C, C.xo);
+    ell_absmax_r<KF>(P.eA, iA, kfA, v, er, C, C.zo);
+    if constexpr (STAMPS) {
+      TSYNC(er[RM - 1]);
+      T_END(T_SC0, t_s0);
+    }
+    T_BEGIN_IF(STAMPS, t_s1);
 #pragma unroll
     for (int r = 0; r < RN; ++r) {
-      const int j = lane + 64 * r;
+      const int j = lane + 64 * (r + C.xo);
       const double d = j < n ? dmaxd(dp[r], da[r]) : 0.0;
       dt[r] = 1. / sqrt(limit_scaling(d));
       if (j < n) v[P.S_DT + j] = dt[r];
     }
 #pragma unroll
     for (int r = 0; r < RM; ++r) {
-      const int i = lane + 64 * r;
+      const int i = lane + 64 * (r + C.zo);
       const double e = i < m ? er[r] : 0.0;
       et[r] = 1. / sqrt(limit_scaling(e));
       if (i < m) v[P.S_ET + i] = et[r];
     }
-    LDS_FENCE();
-    TSYNC(et[RM - 1]);
-    T_END(T_SC1, t_s1);
-    T_BEGIN(t_s2);
-    scale_pa_r(v, P.S_P, P.nnzP, P.nnzP + P.nnzA, ra, ca, cprev, lane);
+    C.sync(p, v);  // every column / row factor written before any value is rescaled
+    if constexpr (STAMPS) {
+      TSYNC(et[RM - 1]);
+      T_END(T_SC1, t_s1);
+    }
+    T_BEGIN_IF(STAMPS, t_s2);
+    scale_pa_r(v, P.S_P, P.nnzP, P.nnzP + P.nnzA, ra, ca, cprev, lane, j0);
 #pragma unroll
     for (int r = 0; r < RN; ++r) {
       S.q[r] = dt[r] * S.q[r];
@@ -1794,34 +1828,41 @@ __device__ __forceinline__ void scale_problem(const KParams& p, int inst, const 
     }
 #pragma unroll
     for (int r = 0; r < RM; ++r) E[r] = E[r] * et[r];
-    LDS_FENCE();
-    TSYNC(E[RM - 1]);
-    T_END(T_SC2, t_s2);
-    T_BEGIN(t_s3);
+    // the rescaled values before the cost normalisation's column norms (and the next pass's factors
+    // are not written before every value of this pass is rescaled)
+    C.sync(p, v);
+    if constexpr (STAMPS) {
+      TSYNC(E[RM - 1]);
+      T_END(T_SC2, t_s2);
+    }
+    T_BEGIN_IF(STAMPS, t_s3);
     // cost normalization: mean of P's column norms, |q|_inf
-    ell_absmax_r<KF>(P.eP, iP, kfP, v, dpc, C, 0);
-    // vec_mean of the column norms, summed in index order (staged in the D_temp slots: this
-    // pass's factors are consumed) -- unless a tree sum shows it below |q|_inf by more than the
-    // summation orders can differ (sum_slack; the norms are >= 0): then max(mean, |q|_inf) does
-    // not depend on it
+    ell_absmax_r<KF>(P.eP, iP, kfP, v, dpc, C, C.xo);
+    // vec_mean of the column norms, summed in index order (every wave stages its columns in the
+    // D_temp slots: this pass's factors are consumed) -- unless a tree sum shows it below |q|_inf
+    // by more than the summation orders can differ (sum_slack; the norms are >= 0): then
+    // max(mean, |q|_inf) does not depend on it
     double qmax = 0.0, csum = 0.0;
 #pragma unroll
     for (int r = 0; r < RN; ++r) {
-      const int j = lane + 64 * r;
+      const int j = lane + 64 * (r + C.xo);
       if (j < n) {
         v[P.S_DT + j] = dpc[r];
         csum = csum + dpc[r];
         qmax = dmaxd(qmax, fabs(S.q[r]));
       }
     }
-    const double inq = limit_scaling(wave_max(qmax));
-    const double T = wave_sum(csum);
+    const double mine[2] = {wave_sum(csum), wave_max(qmax)};
+    const bool ks[2] = {true, false};
+    double both[2];
+    C.template all<2>(p, v, mine, ks, both);  // two waves: its barrier publishes the staged norms
+    const double inq = limit_scaling(both[1]), T = both[0];
     double c_temp = inq;
     if (!((T + sum_slack(T, n)) / n < inq)) {
-      LDS_FENCE();
+      if constexpr (Cx::WAVES == 1) LDS_FENCE();  // two waves: the exchange's barrier
       c_temp = seq_sum(v + P.S_DT, n) / n;
-      LDS_FENCE();
-      T_COUNT(T_SCC);
+      C.sync(p, v);  // every wave's reads before the next pass writes its factors there
+      if constexpr (STAMPS) T_COUNT(T_SCC);
     }
     c_temp = limit_scaling(dmaxd(c_temp, inq));
     c_temp = 1. / c_temp;
@@ -1829,27 +1870,31 @@ __device__ __forceinline__ void scale_problem(const KParams& p, int inst, const 
 #pragma unroll
     for (int r = 0; r < RN; ++r) S.q[r] = S.q[r] * c_temp;
     S.c = S.c * c_temp;
-    LDS_FENCE();
-    TSYNC(S.c);
-    T_END(T_SC3, t_s3);
+    if constexpr (Cx::WAVES == 1) LDS_FENCE();
+    if constexpr (STAMPS) {
+      TSYNC(S.c);
+      T_END(T_SC3, t_s3);
+    }
   }
-  for (int k = lane; k < P.nnzP; k += 64) v[P.S_P + k] = v[P.S_P + k] * cprev;
-  LDS_FENCE();
+  for (int k = tid; k < P.nnzP; k += Cx::THREADS) v[P.S_P + k] = v[P.S_P + k] * cprev;
+  if constexpr (Cx::WAVES == 1) LDS_FENCE();  // two waves: the sync below
   // the next solve's data (scaling.c unscale_data): q <- (q c^-1) D^-1, P <- ((P c^-1) D^-1) D^-1
   // with D^-1 = 1 / D and c^-1 = 1 / c as scale_data leaves them; D^-1 staged in the D_temp slots
   // for the row / column operands of scale_pa_r's layout
+  double* const Pw = dr.out_P(p, inst);
+  double* const qw = dr.out_q(p, inst);
   const double cinv = 1. / S.c;
 #pragma unroll
   for (int r = 0; r < RN; ++r) {
-    const int j = lane + 64 * r;
+    const int j = lane + 64 * (r + C.xo);
     const double di = 1. / D[r];
     if (j < n) {
       v[P.S_DT + j] = di;
       qw[j] = (S.q[r] * cinv) * di;
     }
   }
-  LDS_FENCE();
-  unscale_p_r(v, P.S_P, P.nnzP, ra, ca, cinv, lane, Pw);
+  C.sync(p, v);  // every D^-1 and every final P value before the unscale
+  unscale_p_r(v, P.S_P, P.nnzP, ra, ca, cinv, lane, j0, Pw);
 }
 
 // end of scale_data, the wave's slots: constraint classes, scaled bounds, D / E into the slab
@@ -1893,37 +1938,28 @@ __device__ __forceinline__ void scale_bounds(const KParams& p, int inst, bool re
 // scale_bounds, and the scaled values [P | A] copied from the scaling overlay into the resident MV
 // region of the image (read from there by the residual mat-vecs, certificates, KKT (re)assembly
 // and the objective)
-template <int RN, int RM>
+// mvw: the MV region's base -- the LDS image, or the wave's slab under KM_MVG (one wave only)
+template <class Cx, int RN, int RM>
 __device__ __forceinline__ void scale_finish(const KParams& p, int inst, bool rebound, Inst<RN, RM>& S,
-                                             const Slab& sb, double* v, double* mvw, int lane,
+                                             const Slab& sb, double* v, double* mvw, const Cx& C,
                                              const double (&D)[RN], const double (&E)[RM]) {
   const DevPlan& P = p.pl;
-  scale_bounds(p, inst, rebound, S, sb, One{lane, mvw}, D, E);
+  scale_bounds(p, inst, rebound, S, sb, C, D, E);
   // the scaled values [P | A] stay resident in LDS (MV) for the residuals, certificates,
   // (re)assembly and objective; the scaling overlay they come from is overwritten by the KKT image
-  LDS_FENCE();
-  {
-    const int cnt = P.nnzP + P.nnzA;
-    constexpr int U = 8;
-    for (int k0 = 0; k0 < cnt; k0 += 64 * U) {
-      double x[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int k = k0 + 64 * u + lane;
-        x[u] = v[P.S_P + (k < cnt ? k : 0)];
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int k = k0 + 64 * u + lane;
-        if (k < cnt) mvw[P.MV + k] = x[u];
-      }
-    }
-    if (lane == 0) mvw[P.MVZ] = 0.0;
+  if constexpr (Cx::WAVES == 1) LDS_FENCE();  // two waves: the sync behind the copy
+  const int cnt = P.nnzP + P.nnzA;
+  if constexpr (Cx::WAVES == 1) {  // seam: 8 values in flight per lane / a strided loop
+    load_vals(mvw, P.MV, v + P.S_P, cnt, C.lane);
+  } else {
+    for (int k = C.tid(); k < cnt; k += Cx::THREADS) mvw[P.MV + k] = v[P.S_P + k];
   }
-  LDS_FENCE();
-  // global slab copy (Plan::mv_global): other lanes read these values back -- the stores must be
-  // complete and visible to the wave's later loads (workgroup-scope release/acquire)
-  if (P.mv_slab) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  if (C.first()) mvw[P.MVZ] = 0.0;
+  C.sync(p, v);
+  // seam, KM_MVG: the global slab copy (Plan::mv_global) is read back by other lanes -- the stores
+  // must be complete and visible to the wave's later loads (workgroup-scope release/acquire)
+  if constexpr (Cx::WAVES == 1)
+    if (P.mv_slab) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 }
 
 // The end of a solve: the objective (compute_obj_val), store_solution (NaN without a solution), the
@@ -2028,7 +2064,7 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
   const int n = P.n, m = P.m;
   const Slab sb = slab_of(P, scr);
   double* const mv = MVG ? sb.MV : v;
-  One W{lane, mv};  // the wave context of the shared check path
+  One W{lane, mv};  // the wave context of the shared set-up and check paths
   Inst<RN, RM> S;
   const int hs = p.has_state[inst];
   const Drift dr = drift_of(p, inst);
@@ -2038,9 +2074,9 @@ __device__ __forceinline__ void solve_instance(const KParams& p, int inst, doubl
   T_BEGIN(t_sc);
   {
     double D[RN], E[RM];
-    scale_problem<RN, RM>(p, inst, dr, S, v, lane, D, E TACC_ARG);
+    scale_problem(p, inst, dr, S, v, W, D, E TACC_ARG);
     T_BEGIN(t_sf);
-    scale_finish<RN, RM>(p, inst, dr.rebound, S, sb, v, mv, lane, D, E);
+    scale_finish(p, inst, dr.rebound, S, sb, v, mv, W, D, E);
     // the drift state after this solve, stored once the scaling has read it (kept to the end of
     // the solve it was an SGPR live across the ADMM loop; the two-wave kernel's other wave has
     // read it before the scaling's barriers)

@@ -26,12 +26,15 @@
 // flight across them.
 //
 // What this file holds is what only the two-wave kernel has: the half-record solve steps, the
-// owner-split factorization, Ruiz passes and MV copy (assemble_and_factor2, scale_problem2,
-// scale_finish2), the ADMM loop (solve_instance2) and the kernel.  The wave context Wv with its
-// barrier and exchange, and the check path -- ell_load / ell_apply / ell_mv / load_idx /
-// ell_absmax_r, compute_residuals, check_termination with both certificates, rho_estimate,
-// scale_bounds, store_solution -- are engine.hip's, written once over a wave context and called
-// here with Wv (there with One).
+// owner-split factorization (assemble_and_factor2), the warm-start block and the ADMM loop
+// (solve_instance2) and the kernel.  The wave context Wv with its barrier and exchange, the Ruiz
+// passes -- drift_sel, scale_problem with scale_pa_r / unscale_p_r, scale_finish with
+// scale_bounds -- and the check path -- ell_load / ell_apply / ell_mv / load_idx / ell_absmax_r,
+// compute_residuals, check_termination with both certificates, rho_estimate, store_solution --
+// are engine.hip's, written once over a wave context and called here with Wv (there with One):
+// the owner split above is the context's xo / zo / w, every barrier of those phases its sync().
+// The factorization and the warm start stay twins of the one-wave kernel's: merged, they moved
+// the register allocation of a product kernel past the parent's (DESIGN.md, The shared set-up path).
 
 // ---- solve steps of one wave: its half of the step record (segments 0 + 1 for wave 0, 2 + 3 for
 // wave 1) and its two targets
@@ -151,16 +154,10 @@ __device__ __forceinline__ void half_body_pf(const HalfOps& ops, Rsrc rs, int n,
 }
 #undef MPCQP_HPFSTEP
 
-// ---- per-wave instance state: the owned slots of Inst
-template <int RNH, int RMH>
-using Inst2 = Inst<RNH, RMH>;
-template <int RNH, int RMH>
-using Resid2 = Resid<RNH, RMH>;
-
 // KKT (re)assembly and factorization by both waves (the elimination chain on wave 0)
 template <int RNH, int RMH>
 __device__ __forceinline__ void assemble_and_factor2(const KParams& p, double* v, const Wv& W,
-                                                     const Inst2<RNH, RMH>& S, double sigma) {
+                                                     const Inst<RNH, RMH>& S, double sigma) {
   const DevPlan& P = p.pl;
   const int tid = W.lane + 64 * W.w;
   for (int k = tid; k < P.nnzL; k += 128) v[P.LX + k] = 0.0;
@@ -194,192 +191,6 @@ __device__ __forceinline__ void assemble_and_factor2(const KParams& p, double* v
   }
 }
 
-// Ruiz equilibration (scale_problem of the one-wave kernel), owner-split
-template <int RNH, int RMH>
-__device__ __forceinline__ void scale_problem2(const KParams& p, int inst, const DriftSel& dr, Inst2<RNH, RMH>& S,
-                                               double* v, Wv& W, double (&D)[RNH], double (&E)[RMH]) {
-  const DevPlan& P = p.pl;
-  const int n = P.n, m = P.m, lane = W.lane, tid = lane + 64 * W.w;
-  // OSQP's drifted P / q (drift_of, scale_problem of the one-wave kernel)
-  const double* P_in = dr.in_b < 0 ? setup_row(p.Px, p.Px_stride, inst) : drift_row(p.Pw, dr.in_b, p.B, P.nnzP, inst);
-  const double* q_in = dr.in_b < 0 ? setup_row(p.q, p.q_stride, inst) : drift_row(p.qw, dr.in_b, p.B, n, inst);
-  const double* Ax_in = p.Ax + (size_t)inst * P.nnzA;
-  const double* l_in = p.l + (size_t)inst * m;
-  const double* u_in = p.u + (size_t)inst * m;
-  EllIdx<RNH, ELL_KP> iP;
-  EllIdx<RNH, ELL_KAT> iAt;
-  EllIdx<RMH, ELL_KA> iA;
-  load_idx(P.eP, iP, lane, W.xo);
-  load_idx(P.eAt, iAt, lane, W.xo);
-  load_idx(P.eA, iA, lane, W.zo);
-  // this wave's half of the value overlay's rescale operand slots: value slots j in
-  // [w 2 JWH, (w + 1) 2 JWH) (value k = 64 j + lane), u16 pairs
-  constexpr int JWH = 2 * RNH * 2;  // = 4 RN / 2: the one-wave kernel's JW split in two
-  uint32_t ra[JWH], ca[JWH];
-  {
-    const int j0 = W.w * 2 * JWH;  // first value slot of this wave
-#pragma unroll
-    for (int q = 0; q < JWH / 2; ++q) {
-      ra[2 * q] = ra[2 * q + 1] = ca[2 * q] = ca[2 * q + 1] = 0u;
-      const int jg = j0 + 4 * q;  // four u16 slots per 8-byte load
-      if (jg < P.SJ) {            // wave-uniform
-        const uint2 a = *reinterpret_cast<const uint2*>(P.sra + (size_t)lane * P.SJ + jg);
-        const uint2 c = *reinterpret_cast<const uint2*>(P.sca + (size_t)lane * P.SJ + jg);
-        ra[2 * q] = a.x, ra[2 * q + 1] = a.y, ca[2 * q] = c.x, ca[2 * q + 1] = c.y;
-      }
-    }
-  }
-  if (tid == 0) v[P.S_ZERO] = 0.0;
-  {
-    const int cnt = P.nnzP + P.nnzA;
-    for (int k = tid; k < cnt; k += 128) v[P.S_P + k] = k < P.nnzP ? P_in[k] : Ax_in[k - P.nnzP];
-  }
-#pragma unroll
-  for (int r = 0; r < RNH; ++r) {
-    const int j = lane + 64 * (r + W.xo);
-    S.q[r] = j < n ? q_in[j] : 0.0;
-    D[r] = 1.0;
-  }
-#pragma unroll
-  for (int r = 0; r < RMH; ++r) {
-    const int i = lane + 64 * (r + W.zo);
-    S.l[r] = i < m ? dmaxd(l_in[i], -OSQP_INFTY) : 0.0;
-    S.u[r] = i < m ? dmind(u_in[i], OSQP_INFTY) : 0.0;
-    E[r] = 1.0;
-  }
-  S.c = 1.0;
-  double cprev = 1.0;
-  double dpc[RNH];
-  BAR2_X(v, p.pl.XID);
-  const int scaling = uniform_i(set_row(p, inst)->scaling);
-  for (int it = 0; it < scaling; ++it) {
-    double dp[RNH], da[RNH], er[RMH], dt[RNH], et[RMH];
-    if (it == 0) {
-      ell_absmax_r<false>(P.eP, iP, 0u, v, dp, W, W.xo);
-    } else {
-#pragma unroll
-      for (int r = 0; r < RNH; ++r) dp[r] = cprev * dpc[r];
-    }
-    ell_absmax_r<false>(P.eAt, iAt, 0u, v, da, W, W.xo);
-    ell_absmax_r<false>(P.eA, iA, 0u, v, er, W, W.zo);
-#pragma unroll
-    for (int r = 0; r < RNH; ++r) {
-      const int j = lane + 64 * (r + W.xo);
-      const double d = j < n ? dmaxd(dp[r], da[r]) : 0.0;
-      dt[r] = 1. / sqrt(limit_scaling(d));
-      if (j < n) v[P.S_DT + j] = dt[r];
-    }
-#pragma unroll
-    for (int r = 0; r < RMH; ++r) {
-      const int i = lane + 64 * (r + W.zo);
-      const double e = i < m ? er[r] : 0.0;
-      et[r] = 1. / sqrt(limit_scaling(e));
-      if (i < m) v[P.S_ET + i] = et[r];
-    }
-    BAR2_X(v, p.pl.XID);  // every column / row factor written before any value is rescaled
-    {
-      // values k = 64 (j0 + jl) + lane, jl < 2 JWH: this wave's share of scale_pa_r
-      const int cnt = P.nnzP + P.nnzA, j0 = W.w * 2 * JWH;
-      constexpr int U = 8;
-#pragma unroll
-      for (int jb = 0; jb < 2 * JWH; jb += U) {
-        if (64 * (j0 + jb) >= cnt) break;  // wave-uniform
-        double x[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int jl = jb + u, k = 64 * (j0 + jl) + lane, kc = k < cnt ? k : 0;
-          const double f = k < P.nnzP ? cprev : 1.0;
-          const uint32_t a = (jl & 1) ? (ra[jl / 2] >> 16) : (ra[jl / 2] & 0xffffu);
-          const uint32_t b = (jl & 1) ? (ca[jl / 2] >> 16) : (ca[jl / 2] & 0xffffu);
-          x[u] = ((v[P.S_P + kc] * f) * v[a]) * v[b];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int k = 64 * (j0 + jb + u) + lane;
-          if (k < cnt) v[P.S_P + k] = x[u];
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < RNH; ++r) {
-      S.q[r] = dt[r] * S.q[r];
-      D[r] = D[r] * dt[r];
-    }
-#pragma unroll
-    for (int r = 0; r < RMH; ++r) E[r] = E[r] * et[r];
-    BAR2_X(v, p.pl.XID);  // the rescaled values before the cost normalisation's column norms (and the next
-             // pass's factors are not written before every value of this pass is rescaled)
-    ell_absmax_r<false>(P.eP, iP, 0u, v, dpc, W, W.xo);
-    // vec_mean of the column norms in index order: both waves stage their columns in the D_temp
-    // slots (consumed by the rescale above), the exchange's barrier publishes them
-    double qmax = 0.0, csum = 0.0;
-#pragma unroll
-    for (int r = 0; r < RNH; ++r) {
-      const int j = lane + 64 * (r + W.xo);
-      if (j < n) {
-        v[P.S_DT + j] = dpc[r];
-        csum = csum + dpc[r];
-        qmax = dmaxd(qmax, fabs(S.q[r]));
-      }
-    }
-    const double mine[2] = {wave_sum(csum), wave_max(qmax)};
-    const bool ks[2] = {true, false};
-    double both[2];
-    W.all<2>(p, v, mine, ks, both);  // its barrier publishes both waves' staged norms
-    const double inq = limit_scaling(both[1]), T = both[0];
-    double c_temp = inq;  // the mean matters only above |q|_inf (scale_problem)
-    if (!((T + sum_slack(T, n)) / n < inq)) {
-      c_temp = seq_sum(v + P.S_DT, n) / n;
-      BAR2_X(v, p.pl.XID);  // both waves' reads before the next pass writes its factors there
-    }
-    c_temp = limit_scaling(dmaxd(c_temp, inq));
-    c_temp = 1. / c_temp;
-    cprev = c_temp;
-#pragma unroll
-    for (int r = 0; r < RNH; ++r) S.q[r] = S.q[r] * c_temp;
-    S.c = S.c * c_temp;
-  }
-  for (int k = tid; k < P.nnzP; k += 128) v[P.S_P + k] = v[P.S_P + k] * cprev;
-  // the next solve's unscaled data (scale_problem): D^-1 of this wave's columns in the D_temp slots
-  double* const Pw = drift_row(p.Pw, dr.out_b, p.B, P.nnzP, inst);
-  double* const qw = drift_row(p.qw, dr.out_b, p.B, n, inst);
-  const double cinv = 1. / S.c;
-#pragma unroll
-  for (int r = 0; r < RNH; ++r) {
-    const int j = lane + 64 * (r + W.xo);
-    const double di = 1. / D[r];
-    if (j < n) {
-      v[P.S_DT + j] = di;
-      qw[j] = (S.q[r] * cinv) * di;
-    }
-  }
-  BAR2_X(v, p.pl.XID);  // every D^-1 and every final P value before the unscale
-  {
-    const int j0 = W.w * 2 * JWH;
-#pragma unroll
-    for (int jl = 0; jl < 2 * JWH; ++jl) {
-      if (64 * (j0 + jl) >= P.nnzP) break;  // wave-uniform
-      const int k = 64 * (j0 + jl) + lane;
-      const uint32_t a = (jl & 1) ? (ra[jl / 2] >> 16) : (ra[jl / 2] & 0xffffu);
-      const uint32_t b = (jl & 1) ? (ca[jl / 2] >> 16) : (ca[jl / 2] & 0xffffu);
-      if (k < P.nnzP) Pw[k] = ((v[P.S_P + k] * cinv) * v[a]) * v[b];
-    }
-  }
-}
-
-template <int RNH, int RMH>
-__device__ __forceinline__ void scale_finish2(const KParams& p, int inst, bool rebound, Inst2<RNH, RMH>& S,
-                                              const Slab& sb, double* v, const Wv& W,
-                                              const double (&D)[RNH], const double (&E)[RMH]) {
-  const DevPlan& P = p.pl;
-  const int tid = W.tid();
-  scale_bounds(p, inst, rebound, S, sb, W, D, E);
-  const int cnt = P.nnzP + P.nnzA;
-  for (int k = tid; k < cnt; k += 128) v[P.MV + k] = v[P.S_P + k];
-  if (tid == 0) v[P.MVZ] = 0.0;
-  BAR2_X(v, p.pl.XID);
-}
-
 // MODE: 0 the solve steps split between the waves (Plan::split_steps), 1 the same with the matrix
 // operands read one step ahead (Plan::mat_first), 2 every solve step on wave 0 with the one-wave
 // kernel's full step records and step loop while wave 1 waits (a plan without the split packing):
@@ -389,7 +200,7 @@ __device__ __forceinline__ void solve_instance2(const KParams& p, int inst, doub
   const DevPlan& P = p.pl;
   const int n = P.n, m = P.m, lane = W.lane;
   const Slab sb = slab_of(P, scr);
-  Inst2<RNH, RMH> S;
+  Inst<RNH, RMH> S;  // the owned slots
   const int hs = p.has_state[inst];
   const DriftSel dr = drift_sel(p, inst);
 #ifdef MPCQP_TIMING
@@ -398,8 +209,8 @@ __device__ __forceinline__ void solve_instance2(const KParams& p, int inst, doub
   T_BEGIN(t_sc);
   {
     double D[RNH], E[RMH];
-    scale_problem2<RNH, RMH>(p, inst, dr, S, v, W, D, E);
-    scale_finish2<RNH, RMH>(p, inst, dr.rebound, S, sb, v, W, D, E);
+    scale_problem(p, inst, dr, S, v, W, D, E TACC_ARG);
+    scale_finish(p, inst, dr.rebound, S, sb, v, v, W, D, E);
     // the drift state after this solve, stored once the scaling has read it (kept to the end of
     // the solve it was an SGPR live across the ADMM loop; the two-wave kernel's other wave has
     // read it before the scaling's barriers)
@@ -510,7 +321,7 @@ __device__ __forceinline__ void solve_instance2(const KParams& p, int inst, doub
   bool can_check = false;
   constexpr bool MATPF = MODE == 1, W0STEPS = MODE == 2 || MODE == 3;
   double dx[RNH], dy[RMH];
-  Resid2<RNH, RMH> R;
+  Resid<RNH, RMH> R;
   HalfPipe sp;
 #ifdef MPCQP_PAIR_CHECKS
   const HalfOps hops{v, W.w, PAIRED && W.w == 0, P.XID};
