@@ -21,6 +21,7 @@
  *                                     res.x[(Nx+1)*nx:(Nx+1)*nx+nu] and res.info.status
  *                                     reference src/trajectorySimulate.py:296-314,
  *                                               src/trajectorySimulateC.py:338-356
+ *   mpcqp_polish                   <- the polish step of osqp_solve under settings.polish  [polish]
  *   mpcqp_update_settings          <- prob.update_settings(max_iter=, eps_abs=, ...)
  *                                     [osqp_update_max_iter, osqp_update_eps_abs, ...]
  *   mpcqp_update_rho               <- prob.update_settings(rho=)  [osqp_update_rho]
@@ -142,7 +143,7 @@ int mpcqp_set_data_batched(mpcqp_handle *h, const double *Px, const double *q, c
  *   starts from its own row's rho, clipped to [1e-6, 1e6].
  * mpcqp_update_settings[_batched]: the fields OSQP can update between solves -- max_iter, eps_abs,
  *   eps_rel, eps_prim_inf, eps_dual_inf, alpha, check_termination, warm_start (delta and
- *   polish_refine_iter are stored and unused; polish and scaled_termination must be 0).  The
+ *   polish_refine_iter are stored for mpcqp_polish; polish and scaled_termination must be 0).  The
  *   set-up fields rho, sigma, scaling, adaptive_rho, adaptive_rho_interval and
  *   adaptive_rho_tolerance of the argument are IGNORED: the handle keeps its own.  Iterates,
  *   carried rho and data scaling are kept; legal before mpcqp_set_data.  The shared form on a
@@ -193,6 +194,40 @@ int mpcqp_warm_start(mpcqp_handle *h, const double *x, const double *y);
 /* Solve every instance (warm-started from its previous solve when settings.warm_start).
  * x [B*n], y [B*m] device outputs (unscaled, NaN when no solution exists, as OSQP). */
 int mpcqp_solve(mpcqp_handle *h, double *x, double *y, const mpcqp_info *info);
+
+/* Polishing (OSQP 0.6 polish.c) of the result of the mpcqp_solve that directly precedes it on the
+ * handle: an explicit call, where OSQP runs it inside osqp_solve under settings.polish.  Per
+ * instance, in the scaled space: the active sets are guessed from the carried iterates (row i lower-
+ * active when z_i - l_i < -y_i, upper-active when u_i - z_i < y_i), the reduced KKT system
+ * [[P + delta I, A_act'], [A_act, -delta I]] is factorized once on the handle's own factorization
+ * program and solved for [-q; l | u on the active rows], followed by polish_refine_iter rounds of
+ * iterative refinement against the unregularised matrix; z = A x and y go through the normal-cone
+ * projection, and the polished point is accepted by OSQP's rule (both residuals smaller, or one
+ * smaller while the other ADMM residual is below 1e-10).
+ *   status  [B] device, required: the info.status that solve wrote.  Only instances with
+ *           status[i] == MPCQP_SOLVED that the skip mask does not exclude are attempted (OSQP polishes
+ *           OSQP_SOLVED only); the others get status_polish = 0 and nothing else of theirs is touched.
+ *   x, y    [B*n], [B*m] device, required: the buffers solve wrote.  A polished instance's rows are
+ *           overwritten with the polished unscaled solution, and its carried scaled iterates with the
+ *           polished ones (OSQP overwrites work->x / z / y; rho is kept); an instance whose polish
+ *           is not accepted (status_polish = -1) keeps its rows and its state.  The data scaling and
+ *           everything else a later solve reads stay as the solve left them.
+ *   info    device pointers, any may be NULL; obj_val / pri_res / dua_res / n_low / n_upp are written
+ *           for attempted instances only.
+ * delta and polish_refine_iter are those of the instance's settings row (mpcqp_update_settings
+ * [_batched] updates them); a row with delta <= 0 is MPCQP_E_INVALID, naming the row.  The `polish`
+ * setting itself stays refused.  The handle remembers whether its last operation was a solve: after
+ * any mpcqp_set_data*, mpcqp_update_*, mpcqp_warm_start, mpcqp_set_state, mpcqp_set_settings_batched
+ * or another mpcqp_polish the call returns MPCQP_E_INVALID.  Every error message of this call starts
+ * with "mpcqp_polish".  Asynchronous on the handle's stream, no host synchronisation; the buffers
+ * it needs are allocated at the first call. */
+typedef struct {
+  int32_t *status_polish; /* [B] 1 polished, -1 polish unsuccessful, 0 not attempted */
+  double *obj_val, *pri_res, *dua_res; /* [B] of the solution left in x / y */
+  int32_t *n_low, *n_upp; /* [B] sizes of the two active sets */
+} mpcqp_polish_info;
+int mpcqp_polish(mpcqp_handle *h, const int32_t *status, double *x, double *y,
+                 const mpcqp_polish_info *info);
 
 /* Zero-copy access to the handle's own problem-data buffers (device): Ax [B*nnzA], l, u [B*m].
  * A producer kernel (e.g. mpcqp_cl_configure) may rewrite them in place between solves, on the

@@ -53,7 +53,7 @@ EXPORTED = (
     "mpcqp_update_P_batched", "mpcqp_cl_set_id_period",
     "mpcqp_check_settings", "mpcqp_set_settings_batched", "mpcqp_update_settings",
     "mpcqp_update_settings_batched", "mpcqp_update_rho", "mpcqp_update_rho_batched",
-    "mpcqp_get_settings",
+    "mpcqp_get_settings", "mpcqp_polish",
     "mpcqp_cl_create", "mpcqp_cl_destroy", "mpcqp_cl_configure", "mpcqp_cl_step",
     "mpcqp_cl_set_ids", "mpcqp_cl_set_tracking", "mpcqp_cl_noise", "mpcqp_cl_set_plant", "mpcqp_clc_period",
     "mpcqp_ukf_create", "mpcqp_ukf_destroy", "mpcqp_ukf_step", "mpcqp_plant_rk45",
@@ -64,7 +64,7 @@ EXPORTED = (
 PREDATED = (
     "mpcqp_get_scaling", "mpcqp_check_settings", "mpcqp_set_settings_batched",
     "mpcqp_update_settings", "mpcqp_update_settings_batched", "mpcqp_update_rho",
-    "mpcqp_update_rho_batched", "mpcqp_get_settings",
+    "mpcqp_update_rho_batched", "mpcqp_get_settings", "mpcqp_polish",
 )
 
 STATUS = {
@@ -102,6 +102,11 @@ class Info(C.Structure):
     _fields_ = [("status", C.c_void_p), ("iter", C.c_void_p), ("rho_updates", C.c_void_p),
                 ("obj_val", C.c_void_p), ("pri_res", C.c_void_p), ("dua_res", C.c_void_p),
                 ("rho", C.c_void_p)]
+
+
+class PolishInfo(C.Structure):
+    _fields_ = [("status_polish", C.c_void_p), ("obj_val", C.c_void_p), ("pri_res", C.c_void_p),
+                ("dua_res", C.c_void_p), ("n_low", C.c_void_p), ("n_upp", C.c_void_p)]
 
 
 class ClScenario(C.Structure):
@@ -182,6 +187,7 @@ def lib():
     _sig(L, "mpcqp_update_P_batched", "argtypes", [vp, dp])
     _sig(L, "mpcqp_warm_start", "argtypes", [vp, dp, dp])
     _sig(L, "mpcqp_solve", "argtypes", [vp, dp, dp, C.POINTER(Info)])
+    _sig(L, "mpcqp_polish", "argtypes", [vp, dp, dp, dp, C.POINTER(PolishInfo)])
     _sig(L, "mpcqp_dims", "argtypes", [vp, i32p, i32p, i32p, i32p, i32p])
     _sig(L, "mpcqp_engine_kind", "argtypes", [vp, i32p])
     _sig(L, "mpcqp_schedule_kind", "argtypes", [vp, i32p])

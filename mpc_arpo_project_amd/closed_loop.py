@@ -92,12 +92,14 @@ class BatchClosedLoop:
     (qp_model.cost_variants checks it) with variant, an int array [B]: chaser b runs the weight
     set probs[variant[b]] -- its P, q and constant A values; everything else is the family's and
     runs through the one closed-loop handle.  id_period: mpcqp_cl_set_id_period (chasers whose
-    global ids are a period apart draw the same device noise).
+    global ids are a period apart draw the same device noise).  polish: every step's solved QPs
+    are polished (BatchQP.polish) before the controller reads u0.
     """
 
     def __init__(self, prob, x0, device="cuda", noise=None, noise_seed=123,
                  id_offset=0, noise_source=None, longest_first=False, variant=None, id_period=0,
-                 **settings):
+                 polish=False, **settings):
+        self.polish = bool(polish)
         x0 = np.asarray(x0, dtype=float)
         if x0.ndim != 2 or x0.shape[1] != 4:
             raise ValueError("x0 must have shape (B, 4)")
@@ -224,7 +226,13 @@ class BatchClosedLoop:
 
     def step(self):
         """Solve the current QPs, apply the controller and plant, rebuild the QP data (async)."""
-        return self.step_after_solve(self.qp.solve_async())
+        return self.step_after_solve(self._solve())
+
+    def _solve(self):
+        r = self.qp.solve_async()
+        if self.polish:
+            self.qp.polish(out=r, sync=False)
+        return r
 
     def enable_tracking(self, nsim, dist_tol=0.2, ang_tol=45.0):
         """Keep the per-chaser run summary on the device from now on (call before the first step):
@@ -516,7 +524,7 @@ class BatchClosedLoopC(BatchClosedLoop):
         if self.period_index >= len(self.schedule):
             raise MPCQPError("the simulation horizon is exhausted")
         i0, nsub, t0 = self.schedule[self.period_index]
-        r = self.qp.solve_async()
+        r = self._solve()
         if on_solved is not None:
             on_solved(self.qp.stream)
         self._reorder(r)

@@ -2489,6 +2489,7 @@ __global__ void __launch_bounds__(64, KM == KM_MVG ? 2 : MPCQP_WAVES_PER_EU) qp_
 #endif
 constexpr int PAIR_PIPE = MPCQP_PAIR_PIPE;
 #include "engine_pair.inc"
+#include "engine_polish.inc"
 
 // dst[b][k] = src[k] for every instance b (the drift buffers' start: set_data, update_lin_cost)
 __global__ void bcast_rows_kernel(double* dst, const double* src, int B, int cnt) {
@@ -2660,6 +2661,12 @@ struct mpcqp_handle {
   int kregs = 0, kscratch = 0;  // the launched kernel's registers per lane and scratch bytes
   int block = 64;  // threads per workgroup: 64 per wave of an instance
   kernel_fn kern = nullptr;
+  // polishing (mpcqp_polish): the handle's last operation was a solve; the kernel, its grid and its
+  // per-wave scratch rows, set up at the first polish (polish_setup)
+  bool last_solve = false;
+  polish_fn pkern = nullptr;
+  int pgrid = 0;
+  double* pscratch = nullptr;
 };
 
 // device memory owned by the handle: recorded, and freed by mpcqp_destroy
@@ -2888,6 +2895,7 @@ static int promote(mpcqp_handle* h) {
 static int set_data(mpcqp_handle* h, bool batched, const double* Px, const double* q,
                     const double* Ax, const double* l, const double* u) {
   if (int rc = guard(h, Px && q && Ax && l && u)) return rc;
+  h->last_solve = false;
   if (int rc = batched ? batched_rows(h) : 0) return rc;
   const Plan& pl = h->plan;
   const size_t B = (size_t)h->B, rows = batched ? B : 1;
@@ -2918,6 +2926,7 @@ int mpcqp_set_data_batched(mpcqp_handle* h, const double* Px, const double* q, c
 
 int mpcqp_set_settings_batched(mpcqp_handle* h, const mpcqp_settings* rows) {
   if (int rc = guard(h, rows)) return rc;
+  h->last_solve = false;
   if (int rc = mpcqp_check_settings(rows, h->B)) return rc;  // nothing changed so far
   SettingsBackup old(h);
   if (int rc = settings_rows(h)) return rc;
@@ -2936,6 +2945,7 @@ int mpcqp_set_settings_batched(mpcqp_handle* h, const mpcqp_settings* rows) {
 
 int mpcqp_update_settings(mpcqp_handle* h, const mpcqp_settings* s) {
   if (int rc = guard(h, s)) return rc;
+  h->last_solve = false;
   SettingsBackup old(h);
   if (h->rows.empty()) {
     mpcqp_settings next;
@@ -2953,6 +2963,7 @@ int mpcqp_update_settings(mpcqp_handle* h, const mpcqp_settings* s) {
 
 int mpcqp_update_settings_batched(mpcqp_handle* h, const mpcqp_settings* rows) {
   if (int rc = guard(h, rows)) return rc;
+  h->last_solve = false;
   mpcqp_settings next;
   for (int i = 0; i < h->B; ++i)
     if (int rc = merged_row(h->rows.empty() ? h->set : h->rows[i], rows[i], i, next)) return rc;
@@ -2966,6 +2977,7 @@ int mpcqp_update_settings_batched(mpcqp_handle* h, const mpcqp_settings* rows) {
 // osqp_update_rho: the setting and every instance's carried rho <- the clipped value(s); rho [B]
 // (host) or null: rho_all for every instance
 static int update_rho(mpcqp_handle* h, const double* rho, double rho_all) {
+  h->last_solve = false;
   const size_t B = (size_t)h->B;
   for (size_t i = 0; i < B; ++i)
     if (!((rho ? rho[i] : rho_all) > 0))
@@ -3002,6 +3014,7 @@ int mpcqp_get_settings(const mpcqp_handle* h, mpcqp_settings* rows) {
 
 int mpcqp_update_bounds(mpcqp_handle* h, const double* l, const double* u) {
   if (int rc = guard(h, l && u, "update")) return rc;
+  h->last_solve = false;
   const size_t Bm = (size_t)h->B * h->plan.m;
   HIPCHK(copy_rows(h, h->l, l, Bm));
   HIPCHK(copy_rows(h, h->u, u, Bm));
@@ -3010,6 +3023,7 @@ int mpcqp_update_bounds(mpcqp_handle* h, const double* l, const double* u) {
 
 int mpcqp_update_A(mpcqp_handle* h, const double* Ax) {
   if (int rc = guard(h, Ax, "update")) return rc;
+  h->last_solve = false;
   HIPCHK(copy_rows(h, h->Ax, Ax, (size_t)h->B * h->plan.nnzA));
   // each instance's next solve follows osqp_update_A (unscale, overwrite, rescale: drift_of)
   HIPCHK(hipMemsetD32Async(h->pend, 1, (size_t)h->B, h->stream));
@@ -3018,6 +3032,7 @@ int mpcqp_update_A(mpcqp_handle* h, const double* Ax) {
 
 int mpcqp_update_lin_cost(mpcqp_handle* h, const double* q) {
   if (int rc = guard(h, q, "update")) return rc;
+  h->last_solve = false;
   const int n = h->plan.n;
   HIPCHK(copy_rows(h, h->q, q, n));
   if (h->batched) HIPCHK(bcast_rows(h, h->qB, h->q, n));
@@ -3030,6 +3045,7 @@ int mpcqp_update_lin_cost(mpcqp_handle* h, const double* q) {
 
 int mpcqp_update_lin_cost_batched(mpcqp_handle* h, const double* q) {
   if (int rc = guard(h, q, "update")) return rc;
+  h->last_solve = false;
   if (int rc = promote(h)) return rc;
   // as mpcqp_update_lin_cost, row for row: the set-up q and both drift buffers
   const size_t Bn = (size_t)h->B * h->plan.n;
@@ -3041,6 +3057,7 @@ int mpcqp_update_lin_cost_batched(mpcqp_handle* h, const double* q) {
 
 // osqp_update_P for every instance (update_P_kernel): src_stride 0 = one row for all
 static int update_P(mpcqp_handle* h, const double* Px, int src_stride) {
+  h->last_solve = false;
   const int cnt = h->plan.nnzP;
   const SetupRows s = setup_rows(h, h->batched);
   HIPCHK(launch_1d(h, update_P_kernel, (size_t)h->B * cnt, s.Px, s.Px_stride, h->Pw, Px, src_stride,
@@ -3061,6 +3078,7 @@ int mpcqp_update_P_batched(mpcqp_handle* h, const double* Px) {
 
 int mpcqp_warm_start(mpcqp_handle* h, const double* x, const double* y) {
   if (int rc = guard(h, x && y, "warm start")) return rc;
+  h->last_solve = false;
   const size_t B = (size_t)h->B;
   HIPCHK(copy_rows(h, h->xs, x, B * h->plan.n));
   HIPCHK(copy_rows(h, h->ys, y, B * h->plan.m));
@@ -3072,8 +3090,8 @@ int mpcqp_warm_start(mpcqp_handle* h, const double* x, const double* y) {
   return 0;
 }
 
-int mpcqp_solve(mpcqp_handle* h, double* x, double* y, const mpcqp_info* info) {
-  if (int rc = guard(h, true, "solve")) return rc;
+// the solve kernels' arguments from the handle (mpcqp_polish embeds the same in its own)
+static KParams kernel_params(const mpcqp_handle* h, double* x, double* y) {
   const SetupRows s = setup_rows(h, h->batched);
   KParams p{};
   p.pl = h->dp;
@@ -3087,15 +3105,74 @@ int mpcqp_solve(mpcqp_handle* h, double* x, double* y, const mpcqp_info* info) {
   p.dsel = h->dsel, p.pend = h->pend, p.a_inplace = h->a_inplace ? 1 : 0;
   p.has_state = h->has_state;
   p.x_out = x, p.y_out = y;
-  if (info) p.info = *info;
   p.scratch = h->scratch;
   p.counter = h->counter;
   p.timing = h->timing;
   p.skip = h->skip;
   p.order = h->order;
+  return p;
+}
+
+int mpcqp_solve(mpcqp_handle* h, double* x, double* y, const mpcqp_info* info) {
+  if (int rc = guard(h, true, "solve")) return rc;
+  KParams p = kernel_params(h, x, y);
+  if (info) p.info = *info;
   HIPCHK(hipMemsetAsync(h->counter, 0, 64, h->stream));
   hipLaunchKernelGGL(h->kern, dim3(h->grid), dim3(h->block), h->lds_bytes, h->stream, p);
   HIPCHK(hipGetLastError());
+  h->last_solve = true;
+  return 0;
+}
+
+// The polish kernel of the handle's plan, checked against the register / scratch budget as
+// mpcqp_create checks the solve kernel, its persistent grid (LDS image and registers) and a scratch
+// row per wave: at the first mpcqp_polish, so a handle that never polishes allocates nothing more
+static int polish_setup(mpcqp_handle* h) {
+  const Plan& pl = h->plan;
+  const polish_fn k = select_polish(pl.n, pl.m, pl.paired);
+  if (!k) return set_error(MPCQP_E_UNSUPPORTED, "mpcqp_polish: problem dimensions exceed the instantiated kernels");
+  int dev = 0, ncu = 0, nb = 0;
+  HIPCHK(hipGetDevice(&dev));
+  HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+  HIPCHK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  hipFuncAttributes fa{};
+  HIPCHK(hipFuncGetAttributes(&fa, (const void*)k));
+  if (fa.numRegs > diag_env_int("MPCQP_REG_BUDGET", MPCQP_MAX_KERNEL_REGS) ||
+      (int)fa.localSizeBytes > MPCQP_MAX_KERNEL_SCRATCH)
+    return set_error(MPCQP_E_UNSUPPORTED,
+                     "mpcqp_polish: polish kernel allocates " + std::to_string(fa.numRegs) + " registers / " +
+                         std::to_string(fa.localSizeBytes) + " scratch bytes per lane: above the validated budget");
+  const int lds = h->dp.inst_doubles * 8;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k, 64, lds) != hipSuccess || nb <= 0)
+    return set_error(MPCQP_E_UNSUPPORTED, "mpcqp_polish: kernel does not fit on a CU (LDS/VGPR)");
+  const int grid = std::min(h->B, nb * ncu);
+  if (!dev_alloc(h, h->pscratch,
+                 sizeof(double) * (size_t)grid * polish_row_doubles(pl.n, pl.m, pl.mv_slab, pl.nnzP)))
+    return set_error(MPCQP_E_HIP, "mpcqp_polish: hipMalloc(scratch rows)");
+  h->pgrid = grid;
+  h->pkern = k;
+  return 0;
+}
+
+int mpcqp_polish(mpcqp_handle* h, const int32_t* status, double* x, double* y,
+                 const mpcqp_polish_info* info) {
+  if (!h) return set_error(MPCQP_E_INVALID, "mpcqp_polish: null handle");
+  if (!status || !x || !y) return set_error(MPCQP_E_INVALID, "mpcqp_polish: null argument");
+  if (!h->last_solve)
+    return set_error(MPCQP_E_INVALID, "mpcqp_polish: the handle's last operation is not a solve");
+  for (size_t i = 0; i < std::max<size_t>(h->rows.size(), 1); ++i)
+    if (!((h->rows.empty() ? h->set : h->rows[i]).delta > 0))
+      return set_error(MPCQP_E_INVALID, "mpcqp_polish: row " + std::to_string(i) + ": delta must be positive");
+  if (!h->pkern)
+    if (int rc = polish_setup(h)) return rc;
+  PParams pp{};
+  pp.k = kernel_params(h, x, y);
+  pp.k.scratch = h->pscratch;
+  pp.status = status;
+  if (info) pp.info = *info;
+  hipLaunchKernelGGL(h->pkern, dim3(h->pgrid), dim3(64), h->dp.inst_doubles * 8, h->stream, pp);
+  HIPCHK(hipGetLastError());
+  h->last_solve = false;  // a second polish would start from the polished iterates
   return 0;
 }
 
@@ -3163,6 +3240,7 @@ int mpcqp_get_state(const mpcqp_handle* h, double* xs, double* zs, double* ys, d
 int mpcqp_set_state(mpcqp_handle* h, const double* xs, const double* zs, const double* ys,
                     const double* rho, const int32_t* has_state) {
   if (int rc = guard(h, xs && zs && ys && rho && has_state)) return rc;
+  h->last_solve = false;
   const size_t B = (size_t)h->B;
   const Plan& pl = h->plan;
   HIPCHK(copy_rows(h, h->xs, xs, B * pl.n));

@@ -60,6 +60,18 @@ class SolveResult:
     rho: torch.Tensor
 
 
+@dataclass
+class PolishResult:
+    x: torch.Tensor              # [B, n] the solve's buffer: polished rows overwritten
+    y: torch.Tensor              # [B, m]
+    status_polish: torch.Tensor  # [B] int32: 1 polished, -1 unsuccessful, 0 not attempted
+    obj_val: torch.Tensor        # [B] of the solution left in x / y (NaN where not attempted)
+    pri_res: torch.Tensor
+    dua_res: torch.Tensor
+    n_low: torch.Tensor          # [B] int32 sizes of the two active sets (0 where not attempted)
+    n_upp: torch.Tensor
+
+
 class BatchQP:
     """B OSQP problems with a shared pattern, solved together on one GPU."""
 
@@ -367,12 +379,43 @@ class BatchQP:
                          o.rho.data_ptr())
         check(_lib.lib().mpcqp_solve(self._h, o.x.data_ptr(), o.y.data_ptr(), C.byref(info)),
               "mpcqp_solve")
+        self._last = o
         return o
 
     def solve(self) -> SolveResult:
         o = self.solve_async()
         self.stream.synchronize()
         return o
+
+    def polish(self, status=None, out: SolveResult = None, sync=True) -> PolishResult:
+        """Polish the instances the directly preceding solve solved (mpcqp_polish; OSQP's polish
+        step with each instance's delta / polish_refine_iter).  out: that solve's result (default:
+        the last one), whose x / y rows are overwritten where the polish is accepted; status: the
+        int32 [B] device tensor of its statuses (default: out.status).  Enqueued on the handle's
+        stream; sync=False returns without waiting for it."""
+        o = out if out is not None else getattr(self, "_last", None)
+        if o is None:
+            raise MPCQPError("mpcqp_polish: polish before any solve")
+        st = o.status if status is None else status
+        if st.dtype != torch.int32 or tuple(st.shape) != (self.B,) or not st.is_cuda or \
+                not st.is_contiguous():
+            raise ValueError(f"status must be a contiguous int32 device tensor of shape ({self.B},)")
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            f = dict(dtype=torch.float64, device=self.device)
+            i = dict(dtype=torch.int32, device=self.device)
+            nan = float("nan")
+            r = PolishResult(x=o.x, y=o.y, status_polish=torch.zeros(self.B, **i),
+                             obj_val=torch.full((self.B,), nan, **f),
+                             pri_res=torch.full((self.B,), nan, **f),
+                             dua_res=torch.full((self.B,), nan, **f),
+                             n_low=torch.zeros(self.B, **i), n_upp=torch.zeros(self.B, **i))
+        info = _lib.PolishInfo(r.status_polish.data_ptr(), r.obj_val.data_ptr(), r.pri_res.data_ptr(),
+                               r.dua_res.data_ptr(), r.n_low.data_ptr(), r.n_upp.data_ptr())
+        check(_lib.lib().mpcqp_polish(self._h, st.data_ptr(), o.x.data_ptr(), o.y.data_ptr(),
+                                      C.byref(info)), "mpcqp_polish")
+        if sync:
+            self.stream.synchronize()
+        return r
 
     def schedule_info(self):
         v = [C.c_int32() for _ in range(5)]

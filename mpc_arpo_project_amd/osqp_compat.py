@@ -147,4 +147,22 @@ class OSQP:
                                obj_val=float(r.obj_val[0]), pri_res=float(r.pri_res[0]),
                                dua_res=float(r.dua_res[0]), rho_estimate=float(r.rho[0]),
                                rho_updates=int(r.rho_updates[0]), status_polish=0)
-        return SimpleNamespace(x=r.x[0].cpu().numpy(), y=r.y[0].cpu().numpy(), info=info)
+        self._res = SimpleNamespace(x=r.x[0].cpu().numpy(), y=r.y[0].cpu().numpy(), info=info)
+        return self._res
+
+    def polish(self):
+        """osqp's polish step as an explicit call after solve() (polish=True in setup /
+        update_settings stays refused): mpcqp_polish with the delta and polish_refine_iter in
+        force.  Updates and returns the last result: info.status_polish (1 polished, -1
+        unsuccessful, 0 not attempted: the solve did not end 'solved'), and where polished x, y,
+        info.obj_val, info.pri_res and info.dua_res."""
+        if self._qp is None or getattr(self, "_res", None) is None:
+            raise ValueError("solve must be called first")
+        p = self._qp.polish()
+        res = self._res
+        res.info.status_polish = int(p.status_polish[0])
+        if res.info.status_polish == 1:
+            res.x, res.y = p.x[0].cpu().numpy(), p.y[0].cpu().numpy()
+            res.info.obj_val = float(p.obj_val[0])
+            res.info.pri_res, res.info.dua_res = float(p.pri_res[0]), float(p.dua_res[0])
+        return res

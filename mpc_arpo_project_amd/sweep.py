@@ -52,7 +52,10 @@ solver set, the product of the lists (eps sets eps_abs = eps_rel), under the sam
 conditions and noise; `Sweep(solver_sets=[dict(...), ...])` takes any per-instance setting
 (mpcqp_set_settings_batched).  Each step selects the controller from the solve's status, so the
 iteration budget and the tolerances are controller-tuning knobs: success rate and fallback share
-per set come out of one batch.  With W weight sets and S solver sets the variant of global id g is
+per set come out of one batch.  `--polish` polishes every step's solved QPs on the device
+(mpcqp_polish, OSQP's polish step with the instance's delta / polish_refine_iter) before the
+controller reads u0, so weight sets are compared on optima, not on eps-accurate iterates; off by
+default.  With W weight sets and S solver sets the variant of global id g is
 v = g // G0 = w * S + s (`solver_variant_index`); "variants" lists them in that order.
 
   --noise-stream reference (default): the reference's own noise.  trajectorySimulate re-seeds
@@ -178,11 +181,14 @@ class Sweep:
     def __init__(self, scenario="radial", n_seeds=1, n_ics=1024, Nx=40, noise=(0.75, 0.75, 50),
                  isReject=True, T_final=150.0, rank=0, world=1, device="cuda", shards=2,
                  ic_seed=20250328, noise_seed=123, eps=1e-3, keep_traj=False, x0=None,
-                 noise_source=None, variants=None, weights=None, solver=None, solver_sets=None):
+                 noise_source=None, variants=None, weights=None, solver=None, solver_sets=None,
+                 polish=False):
         """variants: a list of (q_scale, r_scale, rs_scale) weight sets, every scenario once per
         set (module docstring); weights: one such triple for a plain sweep (shared cost data).
         solver_sets: a list of dicts of solver settings, every scenario once per set (and per
-        weight set: v = w * S + s); solver: one such dict for a plain sweep (shared settings)"""
+        weight set: v = w * S + s); solver: one such dict for a plain sweep (shared settings).
+        polish: every step's solved QPs are polished on the device (mpcqp_polish) before the
+        controller reads u0"""
         import torch
 
         from .closed_loop import ShardedClosedLoop
@@ -224,7 +230,7 @@ class Sweep:
         self.nsim = int(self.sim.T_final / self.sim.time_stp)
         self.loop = ShardedClosedLoop(self.prob, X, shards=shards, device=device, id_offset=self.lo,
                                       noise=noise, noise_seed=noise_seed,
-                                      noise_source=noise_source, **settings, **kw)
+                                      noise_source=noise_source, polish=polish, **settings, **kw)
         self.loop.enable_tracking(self.nsim, *self.sim.suc_cond)
         self.traj = None
         if keep_traj:
@@ -413,7 +419,12 @@ def main(argv=None):
                          "the sweep are the product of the two lists (module docstring)")
     ap.add_argument("--eps-list", default=None,
                     help="comma list of tolerances (eps_abs = eps_rel) of the solver sets")
+    ap.add_argument("--polish", action="store_true",
+                    help="polish every step's solved QPs on the device before the controller "
+                         "reads u0 (mpcqp_polish; off: results as without the flag)")
     a = ap.parse_args(argv[1:])
+    if a.polish and a.experiment:
+        ap.error("--polish does not combine with --experiment")
     solver_sets = None
     if a.max_iter or a.eps_list:
         if a.experiment:
@@ -455,7 +466,8 @@ def main(argv=None):
         noise = (noise[0], noise[1], int(noise[2]))
     sw = Sweep(a.scenario, a.seeds, a.ics, Nx=a.nx, noise=noise, isReject=not a.no_reject,
                T_final=a.tfinal, rank=rank, world=world, device=device, shards=a.shards,
-               eps=a.eps, keep_traj=a.traj, variants=variants, solver_sets=solver_sets)
+               eps=a.eps, keep_traj=a.traj, variants=variants, solver_sets=solver_sets,
+               polish=a.polish)
     el = _timed_run(sw, dist, device)
     local_sum = sw.summary()
     S = launch.gather_rows(local_sum, sw.G, rank, world, dist)
@@ -471,6 +483,8 @@ def main(argv=None):
         out.update(scenario=a.scenario, n_gpus=world, seeds=a.seeds, ics=a.ics, nx=a.nx,
                    noise=a.noise, reject=not a.no_reject, steps=sw.steps, seconds=el,
                    scenarios_per_s=sw.G / el, solves_per_s=solved_steps / el)
+        if a.polish:
+            out["polish"] = True
         if variants is not None or solver_sets is not None:
             # v = w * S + s; an entry names its weight set and the solver fields that differ
             nS = sw.S
