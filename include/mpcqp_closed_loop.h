@@ -81,6 +81,31 @@ int mpcqp_cl_step(mpcqp_cl *cl, const int32_t *status, const double *x_sol, int3
 int mpcqp_cl_set_tracking(mpcqp_cl *cl, int32_t *iterm, int32_t *success, double *final_err,
                           int32_t *n_fallback, double dist_tol, double ang_tol);
 
+/* The same run summary for the continuous loop, carried by every following mpcqp_clc_period in a
+ * tracked instantiation of its kernel (device buffers success [B], final_err [B], n_fallback [B],
+ * n_ctrl [B*3], all four or none; NULL disables; the caller initialises them to 0).  iterm stays
+ * the argument of mpcqp_clc_period; the caller initialises it to nsimC = int(T_final / T_cont),
+ * the reference's iterm of a run that never terminates.  With x(i) the state at loop index i of
+ * trajectorySimulateC (x(500) = x0; x(i + 1) is the state after the sub-step of index i, the row
+ * traj receives):
+ *   success    1 once a state x(i), 1 <= i < iterm, passes the test above
+ *              (src/trajectorySimulateC.py:426-432).  The reference fills the indices 1 .. 500
+ *              with x0, so x0 is tested once, by the first tracked period; the state that fires
+ *              the termination test, x(iterm), is not tested.
+ *   final_err  |x(iterm - 1) - xr|_2 over the four components; for a chaser that has not
+ *              terminated, of the last state stepped (x(nsimC - 1) at the end of the run)
+ *   n_fallback sample periods whose controller was the failsafe or the deadbeat one (ctrl_seq 2
+ *              or 3); the sub-steps that hold the sample's control are not counted again
+ *   n_ctrl     [b*3 + c]: loop indices 500 <= i < iterm driven by MPC / failsafe / deadbeat
+ *              (c = 0 / 1 / 2), sample and held sub-steps alike: the entries 1 / 2 / 3 of the
+ *              reference's controllerSeq, whose closing continuousAppendIndex gives the index
+ *              nsimC - 1 of an unterminated run to the last period's controller.  (Its last line,
+ *              controllerSeq[-1] = controllerSeq[-2], is not applied: it changes one entry, and
+ *              only when a run terminates on the first sub-step after a sample.)
+ * Frozen chasers (done) are not touched. */
+int mpcqp_clc_set_tracking(mpcqp_cl *cl, int32_t *success, double *final_err, int32_t *n_fallback,
+                           int32_t *n_ctrl, double dist_tol, double ang_tol);
+
 /* Global id of instance 0 of this handle (a rank's shard offset); keys the noise streams. */
 int mpcqp_cl_set_ids(mpcqp_cl *cl, int64_t id0);
 /* period > 0: the noise stream of instance b is keyed by (id0 + b) % period instead of id0 + b, so

@@ -56,6 +56,7 @@ EXPORTED = (
     "mpcqp_get_settings", "mpcqp_polish",
     "mpcqp_cl_create", "mpcqp_cl_destroy", "mpcqp_cl_configure", "mpcqp_cl_step",
     "mpcqp_cl_set_ids", "mpcqp_cl_set_tracking", "mpcqp_cl_noise", "mpcqp_cl_set_plant", "mpcqp_clc_period",
+    "mpcqp_clc_set_tracking",
     "mpcqp_ukf_create", "mpcqp_ukf_destroy", "mpcqp_ukf_step", "mpcqp_plant_rk45",
 )
 
@@ -220,6 +221,7 @@ def lib():
     _sig(L, "mpcqp_cl_set_plant", "argtypes", [vp, C.POINTER(PlantModel), i32])
     _sig(L, "mpcqp_clc_period", "argtypes", [vp, dp, dp, i32, i32, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp,
                                    dp, C.c_double, C.c_double, i32, i32, dp])
+    _sig(L, "mpcqp_clc_set_tracking", "argtypes", [vp, dp, dp, dp, dp, C.c_double, C.c_double])
     _sig(L, "mpcqp_ukf_create", "argtypes", [C.POINTER(UkfModel), i32, vp, C.POINTER(vp)])
     _sig(L, "mpcqp_ukf_destroy", "argtypes", [vp])
     _sig(L, "mpcqp_ukf_step", "argtypes", [vp, dp, dp, dp, dp, dp, dp])

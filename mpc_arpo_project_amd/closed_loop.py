@@ -222,7 +222,11 @@ class BatchClosedLoop:
             self.aborted.bitwise_or_(bad)
             self.done.bitwise_or_(bad)
             if getattr(self, "_tracking", False):
-                self.iterm.copy_(torch.where(bad > 0, self.steps + 1, self.iterm))
+                self.iterm.copy_(torch.where(bad > 0, self._abort_index(), self.iterm))
+
+    def _abort_index(self):
+        """i_term of a chaser whose estimator failed in the step being enqueued"""
+        return self.steps + 1
 
     def step(self):
         """Solve the current QPs, apply the controller and plant, rebuild the QP data (async)."""
@@ -271,12 +275,12 @@ class BatchClosedLoop:
                           self.n_fallback[:, None].double(), self.aborted[:, None].double()],
                          dim=1)
 
-    def _track_solve(self, r):
+    def _track_solve(self, r, first):
         with torch.cuda.stream(self.qp.stream):
             active = self.done == 0
             self.iters_total += torch.where(active, r.iter, 0).to(torch.int64)
             self.last_status.copy_(torch.where(active, r.status, self.last_status))
-            if self.steps == 0:
+            if first:
                 u = r.x[:, self.u0:self.u0 + 2]
                 self.u0_first.copy_(torch.where(active[:, None], u, self.u0_first))
 
@@ -290,7 +294,7 @@ class BatchClosedLoop:
         """Controller select + plant + QP-data rebuild for a solve already enqueued (async)."""
         L = _lib.lib()
         if getattr(self, "_tracking", False):
-            self._track_solve(r)
+            self._track_solve(r, self.steps == 0)
         self._reorder(r)
         opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         rc = L.mpcqp_cl_step(self._cl, r.status.data_ptr(), r.x.data_ptr(), self.qp.n, self.u0,
@@ -478,17 +482,20 @@ class BatchClosedLoopC(BatchClosedLoop):
 
     `period()` = the solve at a sample instant + the RK45 plant sub-steps up to the next sample
     (+ UKF and QP rebuild when noise is given).  `iterm` holds the loop index at which a chaser's
-    termination test fired (nsimC if it never did).  The continuous-time noise of the reference
+    termination test fired (nsimC if it never did); `enable_tracking()` adds the run summary
+    (`summary()`, `ctrl_counts`).  The continuous-time noise of the reference
     (python-control white_noise with covariance Qcont / 0.001, held for noise_length samples) is
     drawn from the device stream with that covariance; python-control is absent here, so its exact
     draws are not reproduced.
     """
 
-    def __init__(self, prob: MPCProblem, x0, T_cont, T_final, mean_motion, isDeltaV=False,
+    def __init__(self, prob, x0, T_cont, T_final, mean_motion, isDeltaV=False,
                  device="cuda", noise=None, noise_seed=123, id_offset=0, noise_source=None,
                  **settings):
         super().__init__(prob, x0, device=device, noise=None, **settings)
         from .estimation import plant_model
+
+        prob = self.prob  # the family's first problem when a list of weight sets was given
 
         self.T_cont, self.T_final = float(T_cont), float(T_final)
         self.schedule = sample_schedule(prob.T, self.T_cont, self.T_final)
@@ -503,11 +510,36 @@ class BatchClosedLoopC(BatchClosedLoop):
         self._init_noise(noise, noise_seed, noise_source, xest, noise_dt=prob.T * hold)
         self.period_index = 0
 
-    def enable_tracking(self, nsim, dist_tol=0.2, ang_tol=45.0):
-        """Not available for the continuous loop: mpcqp_clc_period keeps i_term (self.iterm) but
-        not the success / final-error / fallback run summary of the discrete loop's tracking."""
-        raise NotImplementedError("run summaries are tracked by the discrete loop only; "
-                                  "BatchClosedLoopC exposes iterm, done and ctrl_seq")
+    def enable_tracking(self, dist_tol=0.2, ang_tol=45.0):
+        """Keep the per-chaser run summary on the device from now on (call before the first
+        period): the reference's run reduction of trajectorySimulateC -- succTraj
+        (src/trajectorySimulateC.py:426-432), the final error |x(iterm - 1) - xr| of
+        test/disturbRejComp.py:88, the fallback sample periods and, in `ctrl_counts`, the entries
+        1 / 2 / 3 of controllerSeq -- carried by the tracked period kernel
+        (mpcqp_clc_set_tracking; no trajectory is written), plus the first MPC input, the last
+        solve status and the total ADMM iterations.  `summary()` packs them in the discrete
+        loop's row layout."""
+        if self.period_index:
+            raise MPCQPError("enable_tracking must precede the first period")
+        i32 = dict(dtype=torch.int32, device=self.device)
+        self.success = torch.zeros(self.B, **i32)
+        self.n_fallback = torch.zeros(self.B, **i32)
+        self.ctrl_counts = torch.zeros(self.B, 3, **i32)  # indices run by MPC, failsafe, deadbeat
+        self.final_err = torch.zeros(self.B, dtype=torch.float64, device=self.device)
+        self.iters_total = torch.zeros(self.B, dtype=torch.int64, device=self.device)
+        self.last_status = torch.zeros(self.B, **i32)
+        self.u0_first = torch.full((self.B, 2), float("nan"), dtype=torch.float64,
+                                   device=self.device)
+        check(_lib.lib().mpcqp_clc_set_tracking(self._cl, self.success.data_ptr(),
+                                                self.final_err.data_ptr(),
+                                                self.n_fallback.data_ptr(),
+                                                self.ctrl_counts.data_ptr(), float(dist_tol),
+                                                float(ang_tol)), "mpcqp_clc_set_tracking")
+        self._tracking = True
+
+    def _abort_index(self):
+        i0, nsub, _ = self.schedule[self.period_index]
+        return i0 + nsub  # the period's sub-steps have run by the time the UKF fails
 
     def _noise_scale(self):
         s = 1.0 / np.sqrt(0.001)
@@ -527,6 +559,8 @@ class BatchClosedLoopC(BatchClosedLoop):
         r = self._solve()
         if on_solved is not None:
             on_solved(self.qp.stream)
+        if getattr(self, "_tracking", False):
+            self._track_solve(r, self.period_index == 0)
         self._reorder(r)
         L = _lib.lib()
         opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
@@ -559,14 +593,21 @@ class ShardedClosedLoopC:
     the unsharded loop: chasers are independent and keep their global ids (device noise streams,
     mpcqp_cl_set_ids)."""
 
-    def __init__(self, prob: MPCProblem, x0, T_cont, T_final, mean_motion, shards=2, device="cuda",
-                 id_offset=0, noise_source=None, **kw):
+    def __init__(self, prob, x0, T_cont, T_final, mean_motion, shards=2, device="cuda",
+                 id_offset=0, noise_source=None, variant=None, **kw):
         x0 = np.asarray(x0, dtype=float)
         B = x0.shape[0]
         S = max(1, min(int(shards), B))
         self.cut = [B * j // S for j in range(S + 1)]
         dev = torch.device(device)
         self._draw_k, self._draw_w = None, None
+        if variant is not None:  # a list of problems: each shard takes its chasers' weight sets
+            variant = np.asarray(variant)
+            if variant.shape != (B,):
+                raise ValueError(f"variant must be an int array of shape ({B},)")
+
+        def shard_variant(j):
+            return {} if variant is None else dict(variant=variant[self.cut[j]:self.cut[j + 1]])
 
         def shard_source(j):
             if noise_source is None:
@@ -583,6 +624,7 @@ class ShardedClosedLoopC:
         self.parts = [BatchClosedLoopC(prob, x0[self.cut[j]:self.cut[j + 1]], T_cont, T_final,
                                        mean_motion, device=dev, id_offset=id_offset + self.cut[j],
                                        stream=sts[j], noise_source=shard_source(j),
+                                       **shard_variant(j),
                                        **shard_settings(kw, B, self.cut[j], self.cut[j + 1]))
                       for j in range(S)]
         self.B = B
@@ -621,6 +663,19 @@ class ShardedClosedLoopC:
     @property
     def iterm(self):
         return self._cat("iterm")
+
+    def enable_tracking(self, dist_tol=0.2, ang_tol=45.0):
+        for c in self.parts:
+            c.enable_tracking(dist_tol, ang_tol)
+
+    SUMMARY_FIELDS = BatchClosedLoop.SUMMARY_FIELDS
+
+    def summary(self):
+        return torch.cat([c.summary() for c in self.parts])  # each waits on its shard's stream
+
+    @property
+    def ctrl_counts(self):
+        return self._cat("ctrl_counts")
 
     @property
     def ctrl_seq(self):

@@ -37,6 +37,14 @@ struct ClDev {
   Track tr;
 };
 
+// per-chaser run summary of the continuous loop (mpcqp_clc_set_tracking), carried by the tracked
+// instantiation of the period kernel; kept out of ClDev so that the other kernels' arguments stay
+struct TrackC {
+  int32_t *success, *n_fallback, *n_ctrl;
+  double* final_err;
+  double dist_tol, ang_tol, rad2deg;
+};
+
 // No FMA contraction in this file's own arithmetic (hipcc contracts a * b + c by default, and
 // __dmul_rn / __dadd_rn are plain operators in ROCm's headers, so they fuse too): the scalar logic
 // below restates numpy / scipy operation by operation, and a fused multiply-add rounds once where
@@ -176,6 +184,22 @@ __device__ __forceinline__ void measure(const double* x, double* z) {
   z[1] = atan2(x[1], x[0]);
 }
 
+// The run summary's view of one state x = x(tr.step) of chaser b, for both loops:
+// tr.success[b] = 1 if the index is >= 1 and x is within dist_tol of xr with approach angle
+// |atan(vy / vx)| <= ang_tol degrees (the reference's success test,
+// src/trajectorySimulate.py:369-376, src/trajectorySimulateC.py:426-432; vx = 0 goes as IEEE
+// division and atan take it: +-inf -> 90 degrees, 0 / 0 -> NaN -> no hit);
+// tr.final_err[b] = |x - xr|_2 over all four components (test/disturbRejComp.py:88)
+__device__ __forceinline__ void track_state(const mpcqp_cl_scenario& s, const double* x,
+                                            const Track& tr, int b) {
+  const double dist = norm2(sub(x[0], s.xr[0]), sub(x[1], s.xr[1]));
+  const double ang = mul(fabs(atan(x[3] / x[2])), tr.rad2deg);
+  if (tr.step >= 1 && dist <= tr.dist_tol && ang <= tr.ang_tol) tr.success[b] = 1;
+  double e[NX];
+  for (int k = 0; k < NX; ++k) e[k] = sub(x[k], s.xr[k]);
+  tr.final_err[b] = norm4(e);
+}
+
 // reference src/trajectorySimulate.py:288-337 for one chaser: controller, plant
 // x+ = Ad x + Bd u_prev + w (one-sample actuation delay, quirk Q1), perfect-state estimate,
 // optional measurement z of x+ and the applied control (the UKF's predict input)
@@ -202,13 +226,7 @@ __global__ void __launch_bounds__(256) cl_step_kernel(ClDev d, const int32_t* st
   if (tr.iterm) {
     // the reference's run reduction (src/trajectorySimulate.py:369-376 success test over the
     // states 1 .. iterm-1 of the run; test/disturbRejComp.py:88 final error |x(iterm-1) - xr|)
-    const double* x = x_true + (size_t)b * NX;
-    const double dist = norm2(sub(x[0], s.xr[0]), sub(x[1], s.xr[1]));
-    const double ang = mul(fabs(atan(x[3] / x[2])), tr.rad2deg);
-    if (tr.step >= 1 && dist <= tr.dist_tol && ang <= tr.ang_tol) tr.success[b] = 1;
-    double e[NX];
-    for (int k = 0; k < NX; ++k) e[k] = sub(x[k], s.xr[k]);
-    tr.final_err[b] = norm4(e);
+    track_state(s, x_true + (size_t)b * NX, tr, b);
     if (seq != 1) tr.n_fallback[b] += 1;
   }
   ctrl_out[(size_t)b * 2] = c0;
@@ -293,72 +311,29 @@ __global__ void __launch_bounds__(256) cl_noise_kernel(int B, uint64_t seed, int
 // Each sub-step: termination test of x(i) (-> done, iterm = i), then
 // x(i+1) = solve_ivp(stateEqnN, (t, t + T_cont), x(i), args=(u,)).y[:, -1] (+ [0, 0, u_prev] at
 // the sample for the delta-v model) + w;  t <- t + T_cont.
-__global__ void __launch_bounds__(64) clc_period_kernel(
-    ClDev d, PlantConsts pc, int isDeltaV, const int32_t* status, const double* x_sol, int n,
-    int u0, double* x_true, double* ctrl_prev, double* xintf, double* xest, int32_t* done,
-    int32_t* iterm, int32_t* ctrl_seq, double* ctrl_out, const double* noise, double* z_out,
-    double* u_applied, double t_start, double dt, int i_start, int nsub, double* traj) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= d.B) return;
-  const mpcqp_cl_scenario& s = d.sc;
-  if (done[b]) {
-    ctrl_seq[b] = 0;
-    return;
-  }
-  const double* xe = xest + (size_t)b * 6;
-  double c0, c1, xi = xintf[b];
-  const int seq = select_control(s, status[b], x_sol + (size_t)b * n + u0, xe, xi, c0, c1);
-  xintf[b] = xi;
-  ctrl_seq[b] = seq;
-  ctrl_out[(size_t)b * 2] = c0;
-  ctrl_out[(size_t)b * 2 + 1] = c1;
-  double* up = ctrl_prev + (size_t)b * NU;
-  const double p0 = up[0], p1 = up[1];
-  if (u_applied) {
-    u_applied[(size_t)b * 2] = p0;
-    u_applied[(size_t)b * 2 + 1] = p1;
-  }
-  double w[NX] = {0, 0, 0, 0};
-  if (noise)
-    for (int i = 0; i < NX; ++i) w[i] = noise[(size_t)b * NX + i];
-  double x[NX];
-  for (int i = 0; i < NX; ++i) x[i] = x_true[(size_t)b * NX + i];
-  double t = t_start;
-  int stop = -1;
-  for (int k = 0; k < nsub; ++k) {
-    if (k > 0 && terminated(s, x)) {
-      stop = i_start + k;
-      break;
-    }
-    const double t1 = add(t, dt);
-    const double ua = isDeltaV ? 0.0 : (k == 0 ? p0 : c0);
-    const double ub = isDeltaV ? 0.0 : (k == 0 ? p1 : c1);
-    rk45_interval(pc, t, t1, x, ua, ub);
-    if (isDeltaV && k == 0) {
-      x[2] = add(x[2], p0);
-      x[3] = add(x[3], p1);
-    }
-    for (int i = 0; i < NX; ++i) x[i] = add(x[i], w[i]);
-    if (traj)
-      for (int i = 0; i < NX; ++i) traj[((size_t)b * nsub + k) * NX + i] = x[i];
-    if (k == 0) {
-      double* xw = xest + (size_t)b * 6;
-      for (int i = 0; i < NX; ++i) xw[i] = x[i];
-      xw[4] = 0.0;
-      xw[5] = 0.0;
-      if (z_out) measure(x, z_out + (size_t)b * 2);
-    }
-    t = t1;
-  }
-  if (stop < 0 && terminated(s, x)) stop = i_start + nsub;
-  if (stop >= 0) {
-    done[b] = 1;
-    iterm[b] = stop;
-  }
-  for (int i = 0; i < NX; ++i) x_true[(size_t)b * NX + i] = x[i];
-  up[0] = c0;
-  up[1] = c1;
-}
+//
+// TRACK: the lane also carries the chaser's run summary (mpcqp_clc_set_tracking) through the
+// period in registers -- read on entry, updated from the state x it holds at every loop index
+// that passes the termination test and from the state it leaves with, written on exit; nothing
+// is read or written per sub-step.  Indices (the reference's xtruePiece / controllerSeq):
+//   * the state at the top of iteration k is x(i_start + k); the first period's k = 0 holds
+//     x(500) = x0, which stands for the indices 1 .. 500 the reference fills with x0; every later
+//     period's k = 0 holds the state its predecessor left with (tested again: an OR);
+//   * the state that fires the termination test is x(iterm) and is not evaluated, so final_err
+//     stays |x(iterm - 1) - xr|; a chaser that goes on leaves with its last state evaluated;
+//   * the period's controller drives the indices i_start .. min(iterm, i_start + nsub) - 1, and
+//     the index nsimC - 1 that no period steps when the run ends unterminated (iterm holds nsimC
+//     on entry): the reference's closing continuousAppendIndex.
+#define CLC_PERIOD_KERNEL clc_period_kernel
+#define CLC_PERIOD_TRACK 0
+#include "clc_period.inc"
+#undef CLC_PERIOD_KERNEL
+#undef CLC_PERIOD_TRACK
+#define CLC_PERIOD_KERNEL clc_period_tracked_kernel
+#define CLC_PERIOD_TRACK 1
+#include "clc_period.inc"
+#undef CLC_PERIOD_KERNEL
+#undef CLC_PERIOD_TRACK
 
 using mpcqp::set_error;
 int launched(const char* entry) {  // the return code of an entry point that has launched its kernel
@@ -378,6 +353,7 @@ struct mpcqp_cl {
   PlantConsts pc{};
   int isDeltaV = 0;
   int32_t steps = 0;  // mpcqp_cl_step calls so far (the loop index of the next step)
+  TrackC trc{};       // mpcqp_clc_set_tracking (success == nullptr: mpcqp_clc_period untracked)
 };
 
 extern "C" {
@@ -489,11 +465,28 @@ int mpcqp_clc_period(mpcqp_cl* cl, const int32_t* status, const double* x_sol, i
       !done || !iterm || !ctrl_seq || !ctrl_out || nsub < 1 || !(dt > 0.0))
     return set_error(MPCQP_E_INVALID, "mpcqp_clc_period: invalid argument or no plant set");
   const int B = cl->d.B;
-  hipLaunchKernelGGL(clc_period_kernel, dim3((B + 63) / 64), dim3(64), 0, cl->stream, cl->d,
-                     cl->pc, cl->isDeltaV, status, x_sol, n, u0_offset, x_true, ctrl_prev, xintf,
-                     xest, done, iterm, ctrl_seq, ctrl_out, noise, z, u_applied, t_start, dt,
-                     i_start, nsub, traj);
+  if (cl->trc.success)
+    hipLaunchKernelGGL(clc_period_tracked_kernel, dim3((B + 63) / 64), dim3(64), 0, cl->stream,
+                       cl->d, cl->pc, cl->isDeltaV, status, x_sol, n, u0_offset, x_true, ctrl_prev,
+                       xintf, xest, done, iterm, ctrl_seq, ctrl_out, noise, z, u_applied, t_start,
+                       dt, i_start, nsub, traj, cl->trc);
+  else
+    hipLaunchKernelGGL(clc_period_kernel, dim3((B + 63) / 64), dim3(64), 0, cl->stream, cl->d,
+                       cl->pc, cl->isDeltaV, status, x_sol, n, u0_offset, x_true, ctrl_prev, xintf,
+                       xest, done, iterm, ctrl_seq, ctrl_out, noise, z, u_applied, t_start, dt,
+                       i_start, nsub, traj);
   return launched("mpcqp_clc_period");
+}
+
+int mpcqp_clc_set_tracking(mpcqp_cl* cl, int32_t* success, double* final_err, int32_t* n_fallback,
+                           int32_t* n_ctrl, double dist_tol, double ang_tol) {
+  if (!cl) return set_error(MPCQP_E_INVALID, "mpcqp_clc_set_tracking: null handle");
+  const bool any = success || final_err || n_fallback || n_ctrl;
+  if (any && !(success && final_err && n_fallback && n_ctrl))
+    return set_error(MPCQP_E_INVALID, "mpcqp_clc_set_tracking: all four buffers or none");
+  cl->trc = TrackC{success, n_fallback, n_ctrl, final_err, dist_tol, ang_tol,
+                   180.0 / 3.141592653589793};  // the reference's (180/np.pi)
+  return 0;
 }
 
 }  // extern "C"

@@ -37,13 +37,14 @@ def radial_scenario(Nx: int = 20, Nc: int = 5, Nb: int = 5, isDeltaV: bool = Fal
 
 
 def in_track_scenario(Nx: int = 20, Nc: int = 5, Nb: int = 5, isReject: bool = False,
-                      noise: Noise = None, x0=(-10., 100., 0., 0.), T_final: int = 150):
+                      noise: Noise = None, x0=(-10., 100., 0., 0.), T_final: int = 150,
+                      isDeltaV: bool = False, T_cont: float = float("nan")):
     """In-track approach (reference test/traj_eval_in_track.py); u_lim made explicit (the script
     omits it, which the reference constructor does not allow)."""
     x0 = np.array(x0, dtype=float)
     xr = np.array([0., 2.5, 0., 0.])
     sim = SimConditions(x0, xr, 2.5, 10 * (np.pi / 180), 1.5, 1.107e-3, 0.5, isReject, (0.2, 45),
-                        noise, True, T_final=T_final)
+                        noise, True, T_cont=T_cont, T_final=T_final, isDeltaV=isDeltaV)
     Q = 8e+02 * sparse.diags([0.2 ** 2., 10 ** 2., 3.8 ** 2, 900])
     R = 1000 ** 2 * sparse.diags([1, 1])
     Rs = 5 ** 2 * sparse.diags([1.5, 1.5, 1, 1, 1e5])

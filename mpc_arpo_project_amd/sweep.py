@@ -58,6 +58,18 @@ controller reads u0, so weight sets are compared on optima, not on eps-accurate 
 default.  With W weight sets and S solver sets the variant of global id g is
 v = g // G0 = w * S + s (`solver_variant_index`); "variants" lists them in that order.
 
+Continuous-time loop: `--continuous` runs the same (noise seed x initial condition) grid through
+trajectorySimulateC's loop (RK45 plant at --t-cont, UKF, sample-and-hold MPC), the experiment of
+test/traj_eval_radialC.py (CONTINUOUS_DEFAULTS: Nx = 40, Noise((0.0012, 0.0012), 50), isReject,
+T_final = 300, T_cont = 1 ms, acceleration input; --delta-v for the impulsive model), on
+ShardedClosedLoopC with the run summary kept by the tracked period kernel
+(mpcqp_clc_set_tracking: no trajectory leaves the device).  The summary rows are the discrete
+sweep's; the JSON line gains "ctrl_index_counts", the loop indices run by the MPC, failsafe and
+deadbeat controllers (the entries 1 / 2 / 3 of the reference's controllerSeq, summed over the
+scenarios), and --out also saves the per-scenario [G, 3] counts.  The continuous noise is the
+device stream with the reference's covariance; python-control is absent, so the reference's exact
+draws are not reproduced.
+
   --noise-stream reference (default): the reference's own noise.  trajectorySimulate re-seeds
         numpy's global generator with 123 at every call (src/trajectorySimulate.py:28) and draws
         noiseVec = sigMat @ normal(0, 1, 4) from it (:268, :352-356), so every Monte-Carlo run of
@@ -87,6 +99,14 @@ FIELDS = ("u0_x", "u0_y", "last_status", "admm_iters", "i_term", "success", "fin
 SCENARIO_DEFAULTS = {
     "radial": dict(nx=40, noise="0.75,0.75,50", reject=True, tfinal=150.0),     # traj_eval_radial.py:23-25,43,57,68
     "in_track": dict(nx=40, noise="none", reject=False, tfinal=100.0),          # traj_eval_in_track.py:40-42,52,62
+}
+
+
+# test/traj_eval_radialC.py:23-25,37-38,46-47,60 (the in-track approach has no continuous script:
+# its discrete settings, over the same horizon)
+CONTINUOUS_DEFAULTS = {
+    "radial": dict(nx=40, noise="0.0012,0.0012,50", reject=True, tfinal=300.0),
+    "in_track": dict(nx=40, noise="none", reject=False, tfinal=300.0),
 }
 
 
@@ -124,19 +144,18 @@ def scenario_states(scenario: str, n_seeds: int, n_ics: int, lo: int, hi: int, i
     return ics[g % n_ics]
 
 
-def build(scenario: str, Nx: int, noise, isReject: bool, T_final: float, weights=None):
+def build(scenario: str, Nx: int, noise, isReject: bool, T_final: float, weights=None,
+          T_cont=float("nan"), isDeltaV=False):
     """(sim, problem) of the approach; weights: (q_scale, r_scale, rs_scale) multipliers of the
-    scenario's Q_state, R_input, R_slack (None: the scenario's own)"""
+    scenario's Q_state, R_input, R_slack (None: the scenario's own); T_cont, isDeltaV: the
+    continuous-time loop's sub-step and input model"""
     from . import qp_model
     from .mpcsim import Noise
 
     nz = None if noise is None else Noise((noise[0], noise[1]), noise[2])
-    if scenario == "radial":
-        sim, mpc, fail, deb = scenarios.radial_scenario(Nx=Nx, isReject=isReject, noise=nz,
-                                                        T_final=T_final)
-    else:
-        sim, mpc, fail, deb = scenarios.in_track_scenario(Nx=Nx, isReject=isReject, noise=nz,
-                                                          T_final=T_final)
+    make = scenarios.radial_scenario if scenario == "radial" else scenarios.in_track_scenario
+    sim, mpc, fail, deb = make(Nx=Nx, isReject=isReject, noise=nz, T_final=T_final, T_cont=T_cont,
+                               isDeltaV=isDeltaV)
     if weights is not None:
         qs, rs, ss = (float(w) for w in weights)
         if min(qs, rs, ss) <= 0:
@@ -182,8 +201,10 @@ class Sweep:
                  isReject=True, T_final=150.0, rank=0, world=1, device="cuda", shards=2,
                  ic_seed=20250328, noise_seed=123, eps=1e-3, keep_traj=False, x0=None,
                  noise_source=None, variants=None, weights=None, solver=None, solver_sets=None,
-                 polish=False):
-        """variants: a list of (q_scale, r_scale, rs_scale) weight sets, every scenario once per
+                 polish=False, T_cont=None, isDeltaV=False):
+        """T_cont: not None runs the continuous-time loop with that sub-step (module docstring;
+        isDeltaV: its impulsive input model); a step of the sweep is then one sample period.
+        variants: a list of (q_scale, r_scale, rs_scale) weight sets, every scenario once per
         set (module docstring); weights: one such triple for a plain sweep (shared cost data).
         solver_sets: a list of dicts of solver settings, every scenario once per set (and per
         weight set: v = w * S + s); solver: one such dict for a plain sweep (shared settings).
@@ -191,8 +212,13 @@ class Sweep:
         controller reads u0"""
         import torch
 
-        from .closed_loop import ShardedClosedLoop
+        from .closed_loop import ShardedClosedLoop, ShardedClosedLoopC
 
+        self.continuous = T_cont is not None
+        if self.continuous and (keep_traj or polish or noise_source is not None):
+            raise ValueError("the continuous sweep keeps summaries only, solves unpolished and "
+                             "draws its noise on the device")
+        mk = dict(T_cont=T_cont, isDeltaV=isDeltaV) if self.continuous else {}
         self.G0 = n_seeds * n_ics
         self.W = 1 if variants is None else len(variants)
         self.S = 1 if solver_sets is None else len(solver_sets)
@@ -211,7 +237,7 @@ class Sweep:
         # the reference's default OSQP tolerances (eps_abs = eps_rel = 1e-3) unless asked otherwise
         settings = dict(eps_abs=eps, eps_rel=eps, **(solver or {}))
         if variants is None and solver_sets is None:
-            self.sim, self.prob = build(scenario, Nx, noise, isReject, T_final, weights)
+            self.sim, self.prob = build(scenario, Nx, noise, isReject, T_final, weights, **mk)
             X = scenario_states(scenario, n_seeds, n_ics, self.lo, self.hi, ic_seed, x0)
         else:
             if noise_source is not None:
@@ -220,18 +246,28 @@ class Sweep:
             X = scenario_states(scenario, n_seeds, n_ics, 0, self.G0, ic_seed, x0)[g0]
             kw = dict(id_period=self.G0)
             if variants is None:
-                self.sim, self.prob = build(scenario, Nx, noise, isReject, T_final, weights)
+                self.sim, self.prob = build(scenario, Nx, noise, isReject, T_final, weights, **mk)
             else:
-                built = [build(scenario, Nx, noise, isReject, T_final, wt) for wt in variants]
+                built = [build(scenario, Nx, noise, isReject, T_final, wt, **mk)
+                         for wt in variants]
                 self.sim, self.prob = built[0][0], [b[1] for b in built]
                 kw["variant"] = w
             if solver_sets is not None:
                 settings.update(solver_set_arrays(solver_sets, s, settings))
-        self.nsim = int(self.sim.T_final / self.sim.time_stp)
-        self.loop = ShardedClosedLoop(self.prob, X, shards=shards, device=device, id_offset=self.lo,
-                                      noise=noise, noise_seed=noise_seed,
-                                      noise_source=noise_source, polish=polish, **settings, **kw)
-        self.loop.enable_tracking(self.nsim, *self.sim.suc_cond)
+        if self.continuous:
+            self.loop = ShardedClosedLoopC(self.prob, X, T_cont, T_final, self.sim.mean_mtn,
+                                           isDeltaV=isDeltaV, shards=shards, device=device,
+                                           id_offset=self.lo, noise=noise, noise_seed=noise_seed,
+                                           **settings, **kw)
+            self.nsim = self.loop.periods
+            self.loop.enable_tracking(*self.sim.suc_cond)
+        else:
+            self.nsim = int(self.sim.T_final / self.sim.time_stp)
+            self.loop = ShardedClosedLoop(self.prob, X, shards=shards, device=device,
+                                          id_offset=self.lo, noise=noise, noise_seed=noise_seed,
+                                          noise_source=noise_source, polish=polish, **settings,
+                                          **kw)
+            self.loop.enable_tracking(self.nsim, *self.sim.suc_cond)
         self.traj = None
         if keep_traj:
             self.traj = torch.empty(self.hi - self.lo, self.nsim + 1, 4, dtype=torch.float64,
@@ -241,8 +277,9 @@ class Sweep:
 
     def run(self, check_every=16):
         """step every chaser until all terminated or the horizon (T_final / T) is reached"""
+        advance = self.loop.period if self.continuous else self.loop.step
         for k in range(self.nsim):
-            self.loop.step()
+            advance()
             self.steps += 1
             if self.traj is not None:
                 self.traj[:, k + 1] = self.loop.x_true
@@ -253,6 +290,10 @@ class Sweep:
 
     def summary(self):
         return self.loop.summary()
+
+    def ctrl_counts(self):
+        """continuous sweeps: [hi - lo, 3] loop indices per controller (float64, as the summary)"""
+        return self.loop.ctrl_counts.double()
 
     def close(self):
         self.loop.close()
@@ -419,12 +460,28 @@ def main(argv=None):
                          "the sweep are the product of the two lists (module docstring)")
     ap.add_argument("--eps-list", default=None,
                     help="comma list of tolerances (eps_abs = eps_rel) of the solver sets")
+    ap.add_argument("--continuous", action="store_true",
+                    help="run the grid through the continuous-time loop (trajectorySimulateC, the "
+                         "experiment of test/traj_eval_radialC.py; defaults: its Nx = 40, noise "
+                         "0.0012,0.0012,50, rejection on).  The noise is the device stream with "
+                         "the reference's continuous covariance: python-control is absent, so the "
+                         "reference's exact draws are not reproduced")
+    ap.add_argument("--t-cont", type=float, default=0.001,
+                    help="--continuous: the plant sub-step T_cont in seconds (reference: 0.001)")
+    ap.add_argument("--t-final", type=float, default=None,
+                    help="--continuous: the simulated time in seconds (reference: 300)")
+    ap.add_argument("--delta-v", action="store_true",
+                    help="--continuous: impulsive delta-v input model instead of acceleration")
     ap.add_argument("--polish", action="store_true",
                     help="polish every step's solved QPs on the device before the controller "
                          "reads u0 (mpcqp_polish; off: results as without the flag)")
     a = ap.parse_args(argv[1:])
     if a.polish and a.experiment:
         ap.error("--polish does not combine with --experiment")
+    if a.continuous and (a.experiment or a.polish or a.traj):
+        ap.error("--continuous does not combine with --experiment, --polish or --traj")
+    if not a.continuous and (a.t_final is not None or a.delta_v):
+        ap.error("--t-final / --delta-v need --continuous")
     solver_sets = None
     if a.max_iter or a.eps_list:
         if a.experiment:
@@ -440,9 +497,11 @@ def main(argv=None):
             ap.error("--q-scale / --r-scale / --rs-scale do not combine with --experiment")
         lists = [[float(x) for x in (v or "1").split(",")] for v in (a.q_scale, a.r_scale, a.rs_scale)]
         variants = [(qs, rs, ss) for qs in lists[0] for rs in lists[1] for ss in lists[2]]
-    dflt = SCENARIO_DEFAULTS[a.scenario]
+    dflt = (CONTINUOUS_DEFAULTS if a.continuous else SCENARIO_DEFAULTS)[a.scenario]
     a.nx = dflt["nx"] if a.nx is None else a.nx
     a.noise = dflt["noise"] if a.noise is None else a.noise
+    if a.continuous and a.t_final is not None:
+        a.tfinal = a.t_final
     a.tfinal = dflt["tfinal"] if a.tfinal is None else a.tfinal
     a.no_reject = not dflt["reject"] if a.reject is None else a.reject == "no"
     if a.gpus > 1 and not launch.launched():
@@ -467,10 +526,11 @@ def main(argv=None):
     sw = Sweep(a.scenario, a.seeds, a.ics, Nx=a.nx, noise=noise, isReject=not a.no_reject,
                T_final=a.tfinal, rank=rank, world=world, device=device, shards=a.shards,
                eps=a.eps, keep_traj=a.traj, variants=variants, solver_sets=solver_sets,
-               polish=a.polish)
+               polish=a.polish, T_cont=a.t_cont if a.continuous else None, isDeltaV=a.delta_v)
     el = _timed_run(sw, dist, device)
     local_sum = sw.summary()
     S = launch.gather_rows(local_sum, sw.G, rank, world, dist)
+    counts = launch.gather_rows(sw.ctrl_counts(), sw.G, rank, world, dist) if a.continuous else None
     traj = gather_traj(sw.traj, sw.G, rank, world, dist) if a.traj else None
     if dist:
         t = torch.tensor([el], dtype=torch.float64, device=device)
@@ -480,11 +540,19 @@ def main(argv=None):
         Sn = S.cpu().numpy()
         out = reduce(Sn)
         solved_steps = float(Sn[:, FIELDS.index("i_term")].sum())
+        if a.continuous:  # i_term counts sub-steps from the literal 500: one solve per period
+            hold = int(sw.sim.time_stp / a.t_cont)
+            solved_steps = float(np.ceil((Sn[:, FIELDS.index("i_term")] - 500) / hold).sum())
         out.update(scenario=a.scenario, n_gpus=world, seeds=a.seeds, ics=a.ics, nx=a.nx,
                    noise=a.noise, reject=not a.no_reject, steps=sw.steps, seconds=el,
                    scenarios_per_s=sw.G / el, solves_per_s=solved_steps / el)
         if a.polish:
             out["polish"] = True
+        if a.continuous:
+            Cn = counts.cpu().numpy()
+            out.update(continuous=True, t_cont=a.t_cont, t_final=a.tfinal, delta_v=a.delta_v,
+                       ctrl_index_counts=dict(zip(("mpc", "failsafe", "deadbeat"),
+                                                  (int(v) for v in Cn.sum(axis=0)))))
         if variants is not None or solver_sets is not None:
             # v = w * S + s; an entry names its weight set and the solver fields that differ
             nS = sw.S
@@ -500,6 +568,8 @@ def main(argv=None):
                 out["variants"].append(dict(**e, **r))
         if a.out:
             np.save(a.out, Sn)
+            if a.continuous:
+                np.save(a.out.replace(".npy", "") + "_ctrl_counts.npy", Cn)
             if traj is not None:
                 np.save(a.out.replace(".npy", "") + "_traj.npy", traj.cpu().numpy())
         print(json.dumps(out), flush=True)
