@@ -22,6 +22,7 @@
  *                                     reference src/trajectorySimulate.py:296-314,
  *                                               src/trajectorySimulateC.py:338-356
  *   mpcqp_polish                   <- the polish step of osqp_solve under settings.polish  [polish]
+ *   mpcqp_adjoint                  <- no OSQP call: the adjoint solve of a differentiable QP layer
  *   mpcqp_update_settings          <- prob.update_settings(max_iter=, eps_abs=, ...)
  *                                     [osqp_update_max_iter, osqp_update_eps_abs, ...]
  *   mpcqp_update_rho               <- prob.update_settings(rho=)  [osqp_update_rho]
@@ -228,6 +229,49 @@ typedef struct {
 } mpcqp_polish_info;
 int mpcqp_polish(mpcqp_handle *h, const int32_t *status, double *x, double *y,
                  const mpcqp_polish_info *info);
+
+/* Adjoint solves: how the solution of every solved instance moves with its data, for a caller's
+ * loss L.  With the active rows act of the carried iterates (the polish's rule; lower: b = l,
+ * upper: b = u) the solution satisfies K [x; y_act] = [-q; b_act], K = [[P, A_act'], [A_act, 0]].
+ * Given gx = dL/dx and optionally gy = dL/dy the call solves K [dx; dy] = [gx; gy_act] (dy = 0 off
+ * act) and returns
+ *   gq = -dx;  gl_i = dy_i on lower-active rows, gu_i = dy_i on upper-active rows, 0 elsewhere;
+ *   gAx_ij = -(y_i dx_j + dy_i x_j) on A's pattern (0 on inactive rows);
+ *   gPx_ii = -dx_i x_i, gPx_ij = -(dx_i x_j + dx_j x_i) for a stored upper entry i < j (it stands
+ *   for both halves).
+ * This is the one-sided derivative on the current active set.  Per instance the last scaling is
+ * redone, the reduced KKT [[P + delta I, A_act'], [A_act, -delta I]] is factorized ONCE on the
+ * handle's factorization program in the scaled space, and each of the nrhs right-hand sides is
+ * solved with `refine` rounds of iterative refinement against the unregularised matrix.
+ *   status  [B] device, required: the info.status that solve wrote.  Instances with status[i] ==
+ *           MPCQP_SOLVED that the skip mask does not exclude are attempted (as in mpcqp_polish); the
+ *           others get status_adjoint = 0, act = 0 and ZEROS in every requested gradient row and res.
+ *   x, y    [B*n], [B*m] device, required: the unscaled solution (solve's or polish's buffers).
+ *           Read, never written.
+ * Valid while the handle's carried iterates and scaling are those of its last mpcqp_solve, or of an
+ * mpcqp_polish of that solve: after any mpcqp_set_data*, mpcqp_update_*, mpcqp_warm_start,
+ * mpcqp_set_state or mpcqp_set_settings_batched the call returns MPCQP_E_INVALID until the next
+ * solve.  The call changes no handle state: it may be repeated (bitwise the same outputs), and a
+ * polish may still follow a solve -> adjoint sequence.  delta is that of the instance's settings
+ * row; a row with delta <= 0 is MPCQP_E_INVALID, naming the row.  Every error message of this call
+ * starts with "mpcqp_adjoint".  Asynchronous on the handle's stream, no host synchronisation; the
+ * buffers it needs are allocated at the first call. */
+typedef struct {
+  int32_t nrhs;        /* 1..8 right-hand sides */
+  int32_t refine;      /* refinement rounds after the first solve, >= 0 */
+  const double *gx;    /* [nrhs][B][n] device, required */
+  const double *gy;    /* [nrhs][B][m] device, NULL = 0 */
+} mpcqp_adjoint_in;
+typedef struct {       /* device, any may be NULL */
+  double *gq;          /* [nrhs][B][n] */
+  double *gl, *gu;     /* [nrhs][B][m] */
+  double *gPx, *gAx;   /* [nrhs][B][nnzP], [nrhs][B][nnzA] */
+  double *res;         /* [nrhs][B] relative residual of the scaled adjoint system after the last round */
+  int8_t *act;         /* [B][m] -1 lower-active, +1 upper-active, 0 inactive */
+  int32_t *status_adjoint; /* [B] 1 done, 0 not attempted */
+} mpcqp_adjoint_out;
+int mpcqp_adjoint(mpcqp_handle *h, const int32_t *status, const double *x, const double *y,
+                  const mpcqp_adjoint_in *in, const mpcqp_adjoint_out *out);
 
 /* Zero-copy access to the handle's own problem-data buffers (device): Ax [B*nnzA], l, u [B*m].
  * A producer kernel (e.g. mpcqp_cl_configure) may rewrite them in place between solves, on the

@@ -53,7 +53,7 @@ EXPORTED = (
     "mpcqp_update_P_batched", "mpcqp_cl_set_id_period",
     "mpcqp_check_settings", "mpcqp_set_settings_batched", "mpcqp_update_settings",
     "mpcqp_update_settings_batched", "mpcqp_update_rho", "mpcqp_update_rho_batched",
-    "mpcqp_get_settings", "mpcqp_polish",
+    "mpcqp_get_settings", "mpcqp_polish", "mpcqp_adjoint",
     "mpcqp_cl_create", "mpcqp_cl_destroy", "mpcqp_cl_configure", "mpcqp_cl_step",
     "mpcqp_cl_set_ids", "mpcqp_cl_set_tracking", "mpcqp_cl_noise", "mpcqp_cl_set_plant", "mpcqp_clc_period",
     "mpcqp_clc_set_tracking",
@@ -65,7 +65,7 @@ EXPORTED = (
 PREDATED = (
     "mpcqp_get_scaling", "mpcqp_check_settings", "mpcqp_set_settings_batched",
     "mpcqp_update_settings", "mpcqp_update_settings_batched", "mpcqp_update_rho",
-    "mpcqp_update_rho_batched", "mpcqp_get_settings", "mpcqp_polish",
+    "mpcqp_update_rho_batched", "mpcqp_get_settings", "mpcqp_polish", "mpcqp_adjoint",
 )
 
 STATUS = {
@@ -108,6 +108,16 @@ class Info(C.Structure):
 class PolishInfo(C.Structure):
     _fields_ = [("status_polish", C.c_void_p), ("obj_val", C.c_void_p), ("pri_res", C.c_void_p),
                 ("dua_res", C.c_void_p), ("n_low", C.c_void_p), ("n_upp", C.c_void_p)]
+
+
+class AdjointIn(C.Structure):
+    _fields_ = [("nrhs", C.c_int32), ("refine", C.c_int32), ("gx", C.c_void_p), ("gy", C.c_void_p)]
+
+
+class AdjointOut(C.Structure):
+    _fields_ = [("gq", C.c_void_p), ("gl", C.c_void_p), ("gu", C.c_void_p), ("gPx", C.c_void_p),
+                ("gAx", C.c_void_p), ("res", C.c_void_p), ("act", C.c_void_p),
+                ("status_adjoint", C.c_void_p)]
 
 
 class ClScenario(C.Structure):
@@ -189,6 +199,7 @@ def lib():
     _sig(L, "mpcqp_warm_start", "argtypes", [vp, dp, dp])
     _sig(L, "mpcqp_solve", "argtypes", [vp, dp, dp, C.POINTER(Info)])
     _sig(L, "mpcqp_polish", "argtypes", [vp, dp, dp, dp, C.POINTER(PolishInfo)])
+    _sig(L, "mpcqp_adjoint", "argtypes", [vp, dp, dp, dp, C.POINTER(AdjointIn), C.POINTER(AdjointOut)])
     _sig(L, "mpcqp_dims", "argtypes", [vp, i32p, i32p, i32p, i32p, i32p])
     _sig(L, "mpcqp_engine_kind", "argtypes", [vp, i32p])
     _sig(L, "mpcqp_schedule_kind", "argtypes", [vp, i32p])

@@ -2490,6 +2490,7 @@ __global__ void __launch_bounds__(64, KM == KM_MVG ? 2 : MPCQP_WAVES_PER_EU) qp_
 constexpr int PAIR_PIPE = MPCQP_PAIR_PIPE;
 #include "engine_pair.inc"
 #include "engine_polish.inc"
+#include "engine_adjoint.inc"
 
 // dst[b][k] = src[k] for every instance b (the drift buffers' start: set_data, update_lin_cost)
 __global__ void bcast_rows_kernel(double* dst, const double* src, int B, int cnt) {
@@ -2667,6 +2668,12 @@ struct mpcqp_handle {
   polish_fn pkern = nullptr;
   int pgrid = 0;
   double* pscratch = nullptr;
+  // adjoint solves (mpcqp_adjoint): the carried iterates and scaling are those of the last solve
+  // or of a polish of it; the kernel, its grid and its scratch rows, set up at the first call
+  bool adjoint_ok = false;
+  adjoint_fn akern = nullptr;
+  int agrid = 0;
+  double* ascratch = nullptr;
 };
 
 // device memory owned by the handle: recorded, and freed by mpcqp_destroy
@@ -2895,7 +2902,7 @@ static int promote(mpcqp_handle* h) {
 static int set_data(mpcqp_handle* h, bool batched, const double* Px, const double* q,
                     const double* Ax, const double* l, const double* u) {
   if (int rc = guard(h, Px && q && Ax && l && u)) return rc;
-  h->last_solve = false;
+  h->last_solve = h->adjoint_ok = false;
   if (int rc = batched ? batched_rows(h) : 0) return rc;
   const Plan& pl = h->plan;
   const size_t B = (size_t)h->B, rows = batched ? B : 1;
@@ -2926,7 +2933,7 @@ int mpcqp_set_data_batched(mpcqp_handle* h, const double* Px, const double* q, c
 
 int mpcqp_set_settings_batched(mpcqp_handle* h, const mpcqp_settings* rows) {
   if (int rc = guard(h, rows)) return rc;
-  h->last_solve = false;
+  h->last_solve = h->adjoint_ok = false;
   if (int rc = mpcqp_check_settings(rows, h->B)) return rc;  // nothing changed so far
   SettingsBackup old(h);
   if (int rc = settings_rows(h)) return rc;
@@ -2945,7 +2952,7 @@ int mpcqp_set_settings_batched(mpcqp_handle* h, const mpcqp_settings* rows) {
 
 int mpcqp_update_settings(mpcqp_handle* h, const mpcqp_settings* s) {
   if (int rc = guard(h, s)) return rc;
-  h->last_solve = false;
+  h->last_solve = h->adjoint_ok = false;
   SettingsBackup old(h);
   if (h->rows.empty()) {
     mpcqp_settings next;
@@ -2963,7 +2970,7 @@ int mpcqp_update_settings(mpcqp_handle* h, const mpcqp_settings* s) {
 
 int mpcqp_update_settings_batched(mpcqp_handle* h, const mpcqp_settings* rows) {
   if (int rc = guard(h, rows)) return rc;
-  h->last_solve = false;
+  h->last_solve = h->adjoint_ok = false;
   mpcqp_settings next;
   for (int i = 0; i < h->B; ++i)
     if (int rc = merged_row(h->rows.empty() ? h->set : h->rows[i], rows[i], i, next)) return rc;
@@ -2977,7 +2984,7 @@ int mpcqp_update_settings_batched(mpcqp_handle* h, const mpcqp_settings* rows) {
 // osqp_update_rho: the setting and every instance's carried rho <- the clipped value(s); rho [B]
 // (host) or null: rho_all for every instance
 static int update_rho(mpcqp_handle* h, const double* rho, double rho_all) {
-  h->last_solve = false;
+  h->last_solve = h->adjoint_ok = false;
   const size_t B = (size_t)h->B;
   for (size_t i = 0; i < B; ++i)
     if (!((rho ? rho[i] : rho_all) > 0))
@@ -3014,7 +3021,7 @@ int mpcqp_get_settings(const mpcqp_handle* h, mpcqp_settings* rows) {
 
 int mpcqp_update_bounds(mpcqp_handle* h, const double* l, const double* u) {
   if (int rc = guard(h, l && u, "update")) return rc;
-  h->last_solve = false;
+  h->last_solve = h->adjoint_ok = false;
   const size_t Bm = (size_t)h->B * h->plan.m;
   HIPCHK(copy_rows(h, h->l, l, Bm));
   HIPCHK(copy_rows(h, h->u, u, Bm));
@@ -3023,7 +3030,7 @@ int mpcqp_update_bounds(mpcqp_handle* h, const double* l, const double* u) {
 
 int mpcqp_update_A(mpcqp_handle* h, const double* Ax) {
   if (int rc = guard(h, Ax, "update")) return rc;
-  h->last_solve = false;
+  h->last_solve = h->adjoint_ok = false;
   HIPCHK(copy_rows(h, h->Ax, Ax, (size_t)h->B * h->plan.nnzA));
   // each instance's next solve follows osqp_update_A (unscale, overwrite, rescale: drift_of)
   HIPCHK(hipMemsetD32Async(h->pend, 1, (size_t)h->B, h->stream));
@@ -3032,7 +3039,7 @@ int mpcqp_update_A(mpcqp_handle* h, const double* Ax) {
 
 int mpcqp_update_lin_cost(mpcqp_handle* h, const double* q) {
   if (int rc = guard(h, q, "update")) return rc;
-  h->last_solve = false;
+  h->last_solve = h->adjoint_ok = false;
   const int n = h->plan.n;
   HIPCHK(copy_rows(h, h->q, q, n));
   if (h->batched) HIPCHK(bcast_rows(h, h->qB, h->q, n));
@@ -3045,7 +3052,7 @@ int mpcqp_update_lin_cost(mpcqp_handle* h, const double* q) {
 
 int mpcqp_update_lin_cost_batched(mpcqp_handle* h, const double* q) {
   if (int rc = guard(h, q, "update")) return rc;
-  h->last_solve = false;
+  h->last_solve = h->adjoint_ok = false;
   if (int rc = promote(h)) return rc;
   // as mpcqp_update_lin_cost, row for row: the set-up q and both drift buffers
   const size_t Bn = (size_t)h->B * h->plan.n;
@@ -3057,7 +3064,7 @@ int mpcqp_update_lin_cost_batched(mpcqp_handle* h, const double* q) {
 
 // osqp_update_P for every instance (update_P_kernel): src_stride 0 = one row for all
 static int update_P(mpcqp_handle* h, const double* Px, int src_stride) {
-  h->last_solve = false;
+  h->last_solve = h->adjoint_ok = false;
   const int cnt = h->plan.nnzP;
   const SetupRows s = setup_rows(h, h->batched);
   HIPCHK(launch_1d(h, update_P_kernel, (size_t)h->B * cnt, s.Px, s.Px_stride, h->Pw, Px, src_stride,
@@ -3078,7 +3085,7 @@ int mpcqp_update_P_batched(mpcqp_handle* h, const double* Px) {
 
 int mpcqp_warm_start(mpcqp_handle* h, const double* x, const double* y) {
   if (int rc = guard(h, x && y, "warm start")) return rc;
-  h->last_solve = false;
+  h->last_solve = h->adjoint_ok = false;
   const size_t B = (size_t)h->B;
   HIPCHK(copy_rows(h, h->xs, x, B * h->plan.n));
   HIPCHK(copy_rows(h, h->ys, y, B * h->plan.m));
@@ -3120,7 +3127,7 @@ int mpcqp_solve(mpcqp_handle* h, double* x, double* y, const mpcqp_info* info) {
   HIPCHK(hipMemsetAsync(h->counter, 0, 64, h->stream));
   hipLaunchKernelGGL(h->kern, dim3(h->grid), dim3(h->block), h->lds_bytes, h->stream, p);
   HIPCHK(hipGetLastError());
-  h->last_solve = true;
+  h->last_solve = h->adjoint_ok = true;
   return 0;
 }
 
@@ -3173,6 +3180,63 @@ int mpcqp_polish(mpcqp_handle* h, const int32_t* status, double* x, double* y,
   hipLaunchKernelGGL(h->pkern, dim3(h->pgrid), dim3(64), h->dp.inst_doubles * 8, h->stream, pp);
   HIPCHK(hipGetLastError());
   h->last_solve = false;  // a second polish would start from the polished iterates
+  return 0;
+}
+
+// The adjoint kernel of the handle's plan, its persistent grid and a scratch row per wave (the
+// polish's row: the slab and the sink of the redone scaling), as polish_setup: at the first
+// mpcqp_adjoint
+static int adjoint_setup(mpcqp_handle* h) {
+  const Plan& pl = h->plan;
+  const adjoint_fn k = select_adjoint(pl.n, pl.m, pl.paired);
+  if (!k) return set_error(MPCQP_E_UNSUPPORTED, "mpcqp_adjoint: problem dimensions exceed the instantiated kernels");
+  int dev = 0, ncu = 0, nb = 0;
+  HIPCHK(hipGetDevice(&dev));
+  HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+  HIPCHK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  hipFuncAttributes fa{};
+  HIPCHK(hipFuncGetAttributes(&fa, (const void*)k));
+  if (fa.numRegs > diag_env_int("MPCQP_REG_BUDGET", MPCQP_MAX_KERNEL_REGS) ||
+      (int)fa.localSizeBytes > MPCQP_MAX_KERNEL_SCRATCH)
+    return set_error(MPCQP_E_UNSUPPORTED,
+                     "mpcqp_adjoint: adjoint kernel allocates " + std::to_string(fa.numRegs) + " registers / " +
+                         std::to_string(fa.localSizeBytes) + " scratch bytes per lane: above the validated budget");
+  const int lds = h->dp.inst_doubles * 8;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k, 64, lds) != hipSuccess || nb <= 0)
+    return set_error(MPCQP_E_UNSUPPORTED, "mpcqp_adjoint: kernel does not fit on a CU (LDS/VGPR)");
+  const int grid = std::min(h->B, nb * ncu);
+  if (!dev_alloc(h, h->ascratch,
+                 sizeof(double) * (size_t)grid * polish_row_doubles(pl.n, pl.m, pl.mv_slab, pl.nnzP)))
+    return set_error(MPCQP_E_HIP, "mpcqp_adjoint: hipMalloc(scratch rows)");
+  h->agrid = grid;
+  h->akern = k;
+  return 0;
+}
+
+int mpcqp_adjoint(mpcqp_handle* h, const int32_t* status, const double* x, const double* y,
+                  const mpcqp_adjoint_in* in, const mpcqp_adjoint_out* out) {
+  if (!h) return set_error(MPCQP_E_INVALID, "mpcqp_adjoint: null handle");
+  if (!status || !x || !y || !in || !out || !in->gx)
+    return set_error(MPCQP_E_INVALID, "mpcqp_adjoint: null argument");
+  if (in->nrhs < 1 || in->nrhs > 8)
+    return set_error(MPCQP_E_INVALID, "mpcqp_adjoint: nrhs must be 1..8, got " + std::to_string(in->nrhs));
+  if (in->refine < 0)
+    return set_error(MPCQP_E_INVALID, "mpcqp_adjoint: refine must not be negative");
+  if (!h->adjoint_ok)
+    return set_error(MPCQP_E_INVALID,
+                     "mpcqp_adjoint: the handle's carried state is not that of its last solve");
+  for (size_t i = 0; i < std::max<size_t>(h->rows.size(), 1); ++i)
+    if (!((h->rows.empty() ? h->set : h->rows[i]).delta > 0))
+      return set_error(MPCQP_E_INVALID, "mpcqp_adjoint: row " + std::to_string(i) + ": delta must be positive");
+  if (!h->akern)
+    if (int rc = adjoint_setup(h)) return rc;
+  AParams ap{};
+  ap.k = kernel_params(h, nullptr, nullptr);
+  ap.k.scratch = h->ascratch;
+  ap.status = status, ap.x = x, ap.y = y;
+  ap.in = *in, ap.out = *out;
+  hipLaunchKernelGGL(h->akern, dim3(h->agrid), dim3(64), h->dp.inst_doubles * 8, h->stream, ap);
+  HIPCHK(hipGetLastError());
   return 0;
 }
 
@@ -3240,7 +3304,7 @@ int mpcqp_get_state(const mpcqp_handle* h, double* xs, double* zs, double* ys, d
 int mpcqp_set_state(mpcqp_handle* h, const double* xs, const double* zs, const double* ys,
                     const double* rho, const int32_t* has_state) {
   if (int rc = guard(h, xs && zs && ys && rho && has_state)) return rc;
-  h->last_solve = false;
+  h->last_solve = h->adjoint_ok = false;
   const size_t B = (size_t)h->B;
   const Plan& pl = h->plan;
   HIPCHK(copy_rows(h, h->xs, xs, B * pl.n));

@@ -1,0 +1,59 @@
+"""The batched QP solve as a differentiable torch operation.
+
+`qp_solve(qp, q, l, u, Ax=None, Px=None)` solves `qp`'s batch for the given data and returns the
+unscaled x [B, n] and y [B, m]; torch.autograd carries a loss on them back to the data through one
+adjoint launch (BatchQP.adjoint, mpcqp_adjoint): the one-sided derivative on the solution's active
+set, as in every QP layer.  Instances the solve did not solve contribute zero gradients.
+
+The backward contract: q, l, u, Ax, Px are per instance ([B, .]); a shared 1-D q or Px receives
+the sum over the batch.  One backward per forward: the adjoint reads the state the handle carries,
+so it must run before the handle's next data, state or settings call (a later call makes backward
+raise MPCQPError; retain_graph does not lift that).
+"""
+from __future__ import annotations
+
+import torch
+
+from ._lib import MPCQPError
+from .engine import BatchQP
+
+
+class _QPSolve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qp: BatchQP, polish: bool, q, l, u, Ax, Px):
+        if qp._has_data:
+            qp.update(q=q, l=l, u=u, Ax=Ax, Px=Px)
+        else:
+            qp.set_data(Px=Px, q=q, Ax=Ax, l=l, u=u)
+        r = qp.solve()
+        if polish:
+            qp.polish()
+        ctx.qp, ctx.result, ctx.solve_id = qp, r, qp._solves
+        ctx.shapes = [None if t is None else t.shape for t in (q, l, u, Ax, Px)]
+        ctx.set_materialize_grads(False)
+        # the handle's output buffers are overwritten by its next solve: hand out copies
+        return r.x.clone(), r.y.clone()
+
+    @staticmethod
+    def backward(ctx, gx, gy):
+        qp, need = ctx.qp, ctx.needs_input_grad[2:]
+        if qp._solves != ctx.solve_id:
+            raise MPCQPError("mpcqp_adjoint: the handle has solved again since this forward")
+        if gx is None:
+            gx = torch.zeros(qp.B, qp.n, dtype=torch.float64, device=qp.device)
+        names = ("gq", "gl", "gu", "gAx", "gPx")
+        a = qp.adjoint(gx, gy, out=ctx.result, want=[k for k, nd in zip(names, need) if nd])
+        grads = []
+        for k, nd, shape in zip(names, need, ctx.shapes):
+            g = getattr(a, k)[0] if nd else None
+            grads.append(g.sum(0) if nd and len(shape) == 1 else g)
+        return (None, None, *grads)
+
+
+def qp_solve(qp: BatchQP, q, l, u, Ax=None, Px=None, polish=True):
+    """Solve qp's batch for q [B, n], l, u [B, m] and optionally Ax [B, nnzA], Px [B, nnzP] (None:
+    the values the handle holds, or those of the matrices it was created from); polish: polish
+    the solved instances before the adjoint (the active set and the accuracy of x, y it gives are
+    what the gradient is taken on).  Returns (x, y), differentiable with respect to the tensors
+    given."""
+    return _QPSolve.apply(qp, bool(polish), q, l, u, Ax, Px)

@@ -72,6 +72,20 @@ class PolishResult:
     n_upp: torch.Tensor
 
 
+@dataclass
+class AdjointResult:
+    """Outputs of BatchQP.adjoint, [nrhs, B, .]; None where not requested.  Rows of instances that
+    were not attempted (status_adjoint 0) are zero."""
+    gq: torch.Tensor             # dL/dq [nrhs, B, n]
+    gl: torch.Tensor             # dL/dl, dL/du [nrhs, B, m]
+    gu: torch.Tensor
+    gPx: torch.Tensor            # dL/dPx [nrhs, B, nnzP] (a stored upper entry stands for both halves)
+    gAx: torch.Tensor            # dL/dAx [nrhs, B, nnzA]
+    res: torch.Tensor            # [nrhs, B] relative residual of the scaled adjoint system
+    act: torch.Tensor            # [B, m] int8: -1 lower-active, +1 upper-active, 0 inactive
+    status_adjoint: torch.Tensor  # [B] int32: 1 done, 0 not attempted
+
+
 class BatchQP:
     """B OSQP problems with a shared pattern, solved together on one GPU."""
 
@@ -111,6 +125,7 @@ class BatchQP:
         self.nnzA = int(self.A.nnz)
         self._has_data = False
         self._out = None
+        self._solves = 0  # solves enqueued so far (diff.qp_solve: one backward per forward)
 
     # -------------------------------------------------------------------------------- helpers
     def _t(self, a, shape, name):
@@ -380,6 +395,7 @@ class BatchQP:
         check(_lib.lib().mpcqp_solve(self._h, o.x.data_ptr(), o.y.data_ptr(), C.byref(info)),
               "mpcqp_solve")
         self._last = o
+        self._solves += 1
         return o
 
     def solve(self) -> SolveResult:
@@ -415,6 +431,64 @@ class BatchQP:
                                       C.byref(info)), "mpcqp_polish")
         if sync:
             self.stream.synchronize()
+        return r
+
+    ADJOINT_OUTPUTS = ("gq", "gl", "gu", "gPx", "gAx")
+
+    def adjoint(self, gx, gy=None, refine=3, status=None, want=("gq", "gl", "gu"),
+                out: SolveResult = None, sync=True) -> AdjointResult:
+        """Adjoint solves of the instances the last solve solved (mpcqp_adjoint): gx = dL/dx
+        [nrhs, B, n] (2-D: nrhs = 1) and optionally gy = dL/dy [nrhs, B, m] give the gradients named
+        in `want` (of gq, gl, gu, gPx, gAx), [nrhs, B, .], with one factorization per instance
+        for all nrhs <= 8 right-hand sides and `refine` rounds of iterative refinement each.  out:
+        the solve's (or its polish's) result, default the last one, whose x / y are read; status
+        defaults to out.status.  Valid after a solve or a polish of it, until the next data, state or
+        settings call; changes no state.  Enqueued on the handle's stream; sync=False returns without
+        waiting for it."""
+        o = out if out is not None else getattr(self, "_last", None)
+        if o is None:
+            raise MPCQPError("mpcqp_adjoint: adjoint before any solve")
+        st = o.status if status is None else status
+        if st.dtype != torch.int32 or tuple(st.shape) != (self.B,) or not st.is_cuda or \
+                not st.is_contiguous():
+            raise ValueError(f"status must be a contiguous int32 device tensor of shape ({self.B},)")
+        unknown = [w for w in want if w not in self.ADJOINT_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown adjoint outputs {unknown}: choose from {self.ADJOINT_OUTPUTS}")
+        gx = torch.as_tensor(gx, dtype=torch.float64, device=self.device)
+        gx = gx.unsqueeze(0) if gx.dim() == 2 else gx
+        if gx.dim() != 3 or tuple(gx.shape[1:]) != (self.B, self.n):
+            raise ValueError(f"gx must have shape (nrhs, {self.B}, {self.n}) or ({self.B}, {self.n})")
+        nrhs = int(gx.shape[0])
+        gx = gx.contiguous()
+        if gy is not None:
+            gy = torch.as_tensor(gy, dtype=torch.float64, device=self.device)
+            gy = gy.unsqueeze(0) if gy.dim() == 2 else gy
+            if tuple(gy.shape) != (nrhs, self.B, self.m):
+                raise ValueError(f"gy must have shape ({nrhs}, {self.B}, {self.m})")
+            gy = gy.contiguous()
+        width = dict(gq=self.n, gl=self.m, gu=self.m, gPx=self.nnzP, gAx=self.nnzA)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))  # gx / gy are complete
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            f = dict(dtype=torch.float64, device=self.device)
+            g = {k: torch.empty(nrhs, self.B, width[k], **f) if k in want else None
+                 for k in self.ADJOINT_OUTPUTS}
+            r = AdjointResult(**g, res=torch.empty(nrhs, self.B, **f),
+                              act=torch.empty(self.B, self.m, dtype=torch.int8, device=self.device),
+                              status_adjoint=torch.empty(self.B, dtype=torch.int32, device=self.device))
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        ain = _lib.AdjointIn(nrhs, int(refine), gx.data_ptr(), ptr(gy))
+        aout = _lib.AdjointOut(*(ptr(g[k]) for k in self.ADJOINT_OUTPUTS), r.res.data_ptr(),
+                               r.act.data_ptr(), r.status_adjoint.data_ptr())
+        check(_lib.lib().mpcqp_adjoint(self._h, st.data_ptr(), o.x.data_ptr(), o.y.data_ptr(),
+                                       C.byref(ain), C.byref(aout)), "mpcqp_adjoint")
+        for t in (gx, gy):
+            if t is not None:
+                t.record_stream(self.stream)
+        if sync:
+            self.stream.synchronize()
+        else:
+            torch.cuda.current_stream(self.device).wait_stream(self.stream)
         return r
 
     def schedule_info(self):

@@ -1,0 +1,244 @@
+"""mpcqp_adjoint: gradients of the solution against a numpy.longdouble reference built on the
+engine's reported active sets, the truthfulness of `res` and the MPC feedback gain on the MPC QP, the
+call contract, and autograd through diff.qp_solve.
+
+The reference: the dense unscaled reduced KKT [[P, A_act'], [A_act, 0]], equilibrated symmetrically
+in longdouble (the same linear system), solved by float64 LU with longdouble iterative refinement to
+a longdouble residual; the first, unrefined float64 solve is the floor a plain fp64 solver reaches
+and the engine gets MARGIN = 10 times the case's worst floor (Adjoint solves: measured)."""
+import numpy as np
+import pytest
+import scipy.linalg as sla
+import scipy.sparse as sp
+import torch
+
+from mpc_arpo_project_amd import _lib, diff
+from mpc_arpo_project_amd._lib import MPCQPError
+from mpc_arpo_project_amd.engine import BatchQP
+
+pytestmark = pytest.mark.gpu
+L = np.longdouble
+MARGIN = 10.0
+OUTS = ("gq", "gl", "gu", "gPx", "gAx")
+
+
+def _random_qp(seed, B):  # tests/test_gpu_random_structures.py::_random_qp
+    rng = np.random.default_rng(500 + seed)
+    n, m = 70 + 13 * seed, 110 + 17 * seed
+    off = rng.uniform(-0.3, 0.3, n - 1)
+    P = sp.diags([off, 2.0 + rng.random(n), off], [-1, 0, 1], format="csc")
+    rows, cols = [], []
+    for i in range(m):
+        for j in rng.choice(n, size=int(rng.integers(2, 6)), replace=False):
+            rows.append(i), cols.append(int(j))
+    A = sp.csc_matrix((np.ones(len(rows)), (rows, cols)), shape=(m, n))
+    A.sum_duplicates()
+    A.sort_indices()
+    q = rng.standard_normal(n)
+    Ax = rng.standard_normal((B, A.nnz))
+    l, u = np.empty((B, m)), np.empty((B, m))
+    for b in range(B):
+        Ab = sp.csc_matrix((Ax[b], A.indices, A.indptr), shape=A.shape)
+        x0 = rng.standard_normal(n)
+        c = Ab @ x0
+        w = rng.uniform(0.1, 1.0, m)
+        eq = rng.random(m) < 0.2
+        w[eq] = 0.0
+        l[b], u[b] = c - w, c + w
+    return P, q, A, Ax, l, u
+
+
+class Ref:
+    """the reduced KKT of one instance on the active rows `act`, equilibrated in longdouble"""
+
+    def __init__(self, qp, Ax, act):
+        self.qp, self.rows, n = qp, np.flatnonzero(act), qp.n
+        Pu = qp.P.toarray()
+        Pf = Pu + np.triu(Pu, 1).T
+        Ar = sp.csc_matrix((Ax, qp.A.indices, qp.A.indptr), shape=qp.A.shape).toarray()[self.rows]
+        k = len(self.rows)
+        self.K = np.block([[Pf, Ar.T], [Ar, np.zeros((k, k))]]).astype(L)
+        self.s = np.ones(n + k, dtype=L)
+        for _ in range(20):
+            nrm = np.max(np.abs(self.K * np.outer(self.s, self.s)), axis=1)
+            self.s /= np.sqrt(np.where(nrm > 0, nrm, 1))
+        self.Ke = self.K * np.outer(self.s, self.s)
+        self.cond, self.cond_eq = np.linalg.cond(self.K.astype(float)), np.linalg.cond(self.Ke.astype(float))
+
+    def rhs(self, gx, gy):  # [nrhs, n], [nrhs, m] or None -> equilibrated right-hand sides, columns
+        gy = np.zeros((len(gx), self.qp.m)) if gy is None else gy
+        return (np.hstack([gx, gy[:, self.rows]]).astype(L) * self.s).T
+
+    def solve(self, be):
+        """(longdouble solution, plain float64 solution) of the unscaled system, columns"""
+        lu = sla.lu_factor(self.Ke.astype(float))
+        d64 = sla.lu_solve(lu, be.astype(float))
+        d = d64.astype(L)
+        for _ in range(6):
+            d += sla.lu_solve(lu, (be - self.Ke @ d).astype(float))
+        return (d.T * self.s).T, (d64.T * self.s).T
+
+    def residual(self, d, be):  # relative, of an unscaled solution [nrhs, n + k], per right-hand side
+        r = be - self.Ke @ (d / self.s).T.astype(L)
+        return np.max(np.abs(r), axis=0) / np.max(np.abs(be), axis=0)
+
+    def grads(self, d, x, y, act):
+        """the contract's formulas on one solution column d, with the instance's x and y"""
+        qp, n = self.qp, self.qp.n
+        dx, dy, ya = d[:n], np.zeros(qp.m, dtype=d.dtype), np.where(act != 0, y, 0)
+        dy[self.rows] = d[n:]
+        Pi, Pj = qp.P.indices, np.repeat(np.arange(n), np.diff(qp.P.indptr))
+        Ai, Aj = qp.A.indices, np.repeat(np.arange(n), np.diff(qp.A.indptr))
+        gP = np.where(Pi == Pj, -dx[Pi] * x[Pi], -(dx[Pi] * x[Pj] + dx[Pj] * x[Pi]))
+        return dict(gq=-dx, gl=np.where(act < 0, dy, 0), gu=np.where(act > 0, dy, 0), gPx=gP,
+                    gAx=-(ya[Ai] * dx[Aj] + dy[Ai] * x[Aj]))
+
+
+def _np(r, names):
+    return {k: getattr(r, k).cpu().numpy() for k in names}
+
+
+def _err(a, b):
+    return float(np.max(np.abs(a - b)) / (np.max(np.abs(b)) or 1.0))
+
+
+@pytest.mark.parametrize("paired", ["1", "0"])
+@pytest.mark.parametrize("seed", [1, 2, 10])
+def test_random_structures_against_longdouble(monkeypatch, seed, paired):
+    monkeypatch.setenv("MPCQP_DIAGNOSTICS", "1")
+    monkeypatch.setenv("MPCQP_PAIRED", paired)
+    B, rng = 16, np.random.default_rng(seed)
+    P, q, A, Ax, l, u = _random_qp(seed, B)
+    qp = BatchQP(P, A, batch=B, eps_abs=1e-6, eps_rel=1e-6)
+    qp.set_data(q=q, Ax=Ax, l=l, u=u)
+    r = qp.solve()
+    before = _np(qp.adjoint(np.zeros((B, qp.n))), ("act",))["act"]
+    pol = _np(qp.polish(), ("status_polish", "n_low", "n_upp", "x", "y"))
+    att = pol["status_polish"] != 0
+    assert np.array_equal((before < 0).sum(1)[att], pol["n_low"][att])
+    assert np.array_equal((before > 0).sum(1)[att], pol["n_upp"][att])
+    gx = np.zeros((3, B, qp.n))
+    gx[0, :, 0], gx[1, :, qp.n - 1], gx[2] = 1.0, 1.0, rng.standard_normal((B, qp.n))
+    gy = rng.standard_normal((3, B, qp.m))
+    names = OUTS + ("res", "act", "status_adjoint")
+    runs = [(None, _np(qp.adjoint(gx, refine=5, want=OUTS), names)),
+            (gy, _np(qp.adjoint(gx, gy, refine=5, want=OUTS), names))]
+    status = r.status.cpu().numpy()
+    assert np.array_equal(runs[0][1]["status_adjoint"], (status == 1).astype(np.int32))
+    unsolved = r.status.clone()
+    unsolved[3] = -2  # rows of an instance that is not attempted are zero
+    z = _np(qp.adjoint(gx, gy, status=unsolved, want=OUTS), names)
+    assert z["status_adjoint"][3] == 0 and not any(z[k][:, 3].any() for k in OUTS + ("res",)) and not z["act"][3].any()
+    floor, worst, res, counted = 0.0, 0.0, 0.0, 0
+    for b in np.flatnonzero(status == 1):
+        ref = Ref(qp, Ax[b], runs[0][1]["act"][b])
+        if pol["status_polish"][b] != 1 or ref.cond > 1e5:
+            continue
+        counted += 1
+        for g, e in runs:
+            d, d64 = ref.solve(ref.rhs(gx[:, b], None if g is None else g[:, b]))
+            for k in range(3):
+                want = ref.grads(d[:, k], pol["x"][b].astype(L), pol["y"][b].astype(L), e["act"][b])
+                plain = ref.grads(d64[:, k], pol["x"][b], pol["y"][b], e["act"][b])
+                floor = max([floor] + [_err(plain[o], want[o]) for o in OUTS])
+                worst = max([worst] + [_err(e[o][k, b], want[o]) for o in OUTS])
+            res = max(res, e["res"][:, b].max())
+    print(f"seed {seed} paired {paired}: counted {counted}, fp64 floor {floor:.2e}, engine {worst:.2e}, res {res:.2e}")
+    assert counted >= 14
+    assert worst <= MARGIN * floor and res <= MARGIN * floor
+
+
+# (a): relative residual of the returned (dx, dy) on the equilibrated unscaled system <= RES_MULT res
+# + the rounding of dx, dy to float64; the multiple absorbs the norm change between the engine's
+# scaled space and the equilibrated one (measured: at most 19 where res is above the rounding).
+# (b): 20 refinement rounds; res is at its plateau after far fewer (Adjoint solves)
+RES_MULT = 100.0
+
+
+@pytest.mark.parametrize("tag,Nx,dv", [("batch_n20", 20, False), ("batch_n40dv", 40, True)])
+def test_mpc_residual_and_gain(golden, tag, Nx, dv):
+    from conftest import problem
+
+    prob, d, B = problem(Nx, dv), golden(tag), 16
+    qp = BatchQP(prob.P, prob.A, batch=B, eps_abs=1e-6, eps_rel=1e-6, polish_refine_iter=20, max_iter=20000)
+    qp.set_data(q=prob.q, Ax=d["Ax"][:B], l=d["l"][:B], u=d["u"][:B])
+    r = qp.solve()
+    pol = _np(qp.polish(), ("status_polish", "x", "y"))
+    gx = np.zeros((prob.nu, B, qp.n))
+    for k in range(prob.nu):
+        gx[k, :, prob.u0_slice.start + k] = 1.0
+    e = _np(qp.adjoint(gx, refine=20), ("gq", "gl", "gu", "res", "act", "status_adjoint"))
+    assert np.array_equal(e["status_adjoint"] == 1, r.status.cpu().numpy() == 1)
+    qualified = 0
+    for b in np.flatnonzero(e["status_adjoint"] == 1):
+        ref = Ref(qp, d["Ax"][b], e["act"][b])
+        be = ref.rhs(gx[:, b], None)
+        de = np.hstack([-e["gq"][:, b], (e["gl"] + e["gu"])[:, b][:, ref.rows]]).astype(L)
+        true = ref.residual(de, be)
+        rounding = 4 * 2.0 ** -52 * np.max(np.abs(ref.Ke) @ np.abs(de / ref.s).T, axis=0) / np.max(np.abs(be), axis=0)
+        print(f"{tag} {b}: cond_eq {ref.cond_eq:.1e} polish {pol['status_polish'][b]} res {e['res'][:, b]} "
+              f"true {true.astype(float)} rounding {rounding.astype(float)}")
+        assert np.all(true <= RES_MULT * e["res"][:, b] + rounding), b
+        if pol["status_polish"][b] != 1 or ref.cond_eq > 1e10:
+            continue
+        qualified += 1
+        sol, s64 = ref.solve(be)
+        rows = [int(np.flatnonzero(ref.rows == i)[0]) + qp.n for i in range(prob.nx)]  # x0 = xhat rows
+        gain, g64, geng = sol[rows].T, s64[rows].T, (e["gl"] + e["gu"])[:, b, :prob.nx]
+        # a u0 at its bound has no gain: where the reference's is below the rounding of the adjoint
+        # solution it is part of, the errors are taken relative to that solution's max-norm
+        big = np.max(np.abs(sol))
+        scale = float(np.max(np.abs(gain)) if np.max(np.abs(gain)) > 2.0 ** -52 * big else big)
+        floor, err = (float(np.max(np.abs(g - gain))) / scale for g in (g64, geng))
+        print(f"{tag} {b}: gain max {float(np.max(np.abs(gain))):.2e} of {float(big):.2e}, floor {floor:.2e} engine {err:.2e}")
+        assert err <= MARGIN * max(floor, 2.0 ** -52), b
+    assert qualified >= 5
+
+
+@pytest.mark.parametrize("case", ["update_bounds", "warm_start", "set_data", "nrhs0", "nrhs9", "delta", "stable"])
+def test_adjoint_contract(golden, prob20, case):
+    d, B = golden("batch_n20"), 16
+    data = dict(q=prob20.q, Ax=d["Ax"][:B], l=d["l"][:B], u=d["u"][:B])
+    qp = BatchQP(prob20.P, prob20.A, batch=B, eps_abs=1e-6, eps_rel=1e-6)
+    qp.set_data(**data)
+    r = qp.solve()
+    gx = torch.ones(1, B, qp.n, dtype=torch.float64, device="cuda")
+    if case == "stable":  # solve -> adjoint -> polish -> adjoint is legal; repeats are bitwise equal
+        twin = BatchQP(prob20.P, prob20.A, batch=B, eps_abs=1e-6, eps_rel=1e-6)
+        twin.set_data(**data)
+        twin.solve()
+        a0, a1 = (_np(qp.adjoint(gx), ("gq", "gl", "gu", "res", "act")) for _ in range(2))
+        assert all(np.array_equal(a0[k], a1[k]) for k in a0) and a0["gq"].any()
+        for h in (qp, twin):  # a solve after an adjoint is bitwise the solve without it
+            h.update(l=data["l"], u=data["u"])
+            h.solve()
+        sa, st = {**qp.get_state(), **qp.get_scaling()}, {**twin.get_state(), **twin.get_scaling()}
+        assert all(torch.equal(sa[k], st[k]) for k in sa)
+        qp.adjoint(gx)
+        qp.polish()
+        assert (_np(qp.adjoint(gx), ("status_adjoint",))["status_adjoint"] == 1).any()
+        return
+    if case in ("nrhs0", "nrhs9"):
+        ain = _lib.AdjointIn(int(case[4:]), 3, gx.data_ptr(), None)
+        rc = _lib.lib().mpcqp_adjoint(qp._h, r.status.data_ptr(), r.x.data_ptr(), r.y.data_ptr(),
+                                      _lib.C.byref(ain), _lib.C.byref(_lib.AdjointOut()))
+        assert rc == -1 and _lib.lib().mpcqp_last_error().decode().startswith("mpcqp_adjoint: nrhs")
+        return
+    dict(update_bounds=lambda: qp.update(l=data["l"], u=data["u"]),
+         warm_start=lambda: qp.warm_start(r.x.nan_to_num(), r.y.nan_to_num()),
+         set_data=lambda: qp.set_data(**data),
+         delta=lambda: (qp.update_settings(delta=np.where(np.arange(B) == 7, 0.0, 1e-6)), qp.solve()))[case]()
+    with pytest.raises(MPCQPError, match=r"\(-1\): mpcqp_adjoint" + (": row 7" if case == "delta" else "")):
+        qp.adjoint(gx)
+
+
+def test_autograd_equals_adjoint():
+    B, f = 4, dict(dtype=torch.float64, device="cuda")
+    P, q, A, Ax, l, u = _random_qp(1, B)
+    qp = BatchQP(P, A, batch=B, eps_abs=1e-6, eps_rel=1e-6)
+    qt, lt, ut = (torch.tensor(np.broadcast_to(a, (B, a.shape[-1])).copy(), requires_grad=True, **f) for a in (q, l, u))
+    w = torch.randn(B, qp.n, generator=torch.Generator("cuda").manual_seed(0), **f)
+    x, _ = diff.qp_solve(qp, qt, lt, ut, Ax=torch.tensor(Ax, **f))
+    grads = torch.autograd.grad((x * w).sum(), (qt, lt, ut))
+    a = qp.adjoint(w)
+    assert a.gq.any() and all(torch.equal(g, t[0]) for g, t in zip(grads, (a.gq, a.gl, a.gu)))
