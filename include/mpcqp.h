@@ -23,6 +23,7 @@
  *                                               src/trajectorySimulateC.py:338-356
  *   mpcqp_polish                   <- the polish step of osqp_solve under settings.polish  [polish]
  *   mpcqp_adjoint                  <- no OSQP call: the adjoint solve of a differentiable QP layer
+ *   mpcqp_tangent                  <- no OSQP call: its forward-mode counterpart (tangents)
  *   mpcqp_update_settings          <- prob.update_settings(max_iter=, eps_abs=, ...)
  *                                     [osqp_update_max_iter, osqp_update_eps_abs, ...]
  *   mpcqp_update_rho               <- prob.update_settings(rho=)  [osqp_update_rho]
@@ -272,6 +273,41 @@ typedef struct {       /* device, any may be NULL */
 } mpcqp_adjoint_out;
 int mpcqp_adjoint(mpcqp_handle *h, const int32_t *status, const double *x, const double *y,
                   const mpcqp_adjoint_in *in, const mpcqp_adjoint_out *out);
+
+/* Forward sensitivities: how the solution of every solved instance moves along up to 8 directions
+ * (dq, dl, du, dA, dP) of its data.  On the active rows act of the carried iterates (as above)
+ *   K [dx; dy_act] = [-(dq + dP x + dA' y); (db - dA x)_act],  K = [[P, A_act'], [A_act, 0]],
+ *   db_i = dl_i on lower-active rows, du_i on upper-active rows,  dy = 0 off act:
+ * the adjoint's matrix, factorized ONCE per instance for all directions, with the right-hand side
+ * assembled on the device from the perturbation (one pass over the nonzeros of P and of A per
+ * direction) and `refine` rounds of iterative refinement per direction.  A closed loop carries
+ * tangents by calling this right after each solve, while its state is on the handle.
+ * status, x, y, the instances attempted, the validity (the same handle state as mpcqp_adjoint: after
+ * a solve or a polish of it, MPCQP_E_INVALID after any data, state or settings call), delta and
+ * the asynchrony are word for word mpcqp_adjoint's.  Instances that are not attempted get
+ * status_tangent = 0, act = 0 and ZEROS in every requested row.  The call changes no handle state:
+ * it may be repeated (bitwise the same outputs), and a polish or an adjoint may still follow.  At
+ * least one of the five perturbations must be given (MPCQP_E_INVALID otherwise).  Every error
+ * message of this call starts with "mpcqp_tangent". */
+typedef struct {
+  int32_t ndir;        /* 1..8 directions */
+  int32_t refine;      /* refinement rounds after the first solve, >= 0 */
+  const double *dq;    /* [ndir][B][n]    device, NULL = 0 */
+  const double *dl, *du; /* [ndir][B][m]  device, NULL = 0 */
+  const double *dAx;   /* [ndir][B][nnzA] device (CSC order), NULL = 0 */
+  const double *dPx;   /* [ndir][B][nnzP] device (upper CSC; an off-diagonal entry stands for both halves), NULL = 0 */
+} mpcqp_tangent_in;
+typedef struct {       /* device, any may be NULL */
+  double *dx;          /* [ndir][B][n] */
+  double *dy;          /* [ndir][B][m], 0 off the active rows */
+  double *dz;          /* [ndir][B][m]  d(Ax) = A dx + dA x */
+  double *dobj;        /* [ndir][B]     d(x'Px/2 + q'x) = x'dP x/2 + dq'x + (Px + q)'dx */
+  double *res;         /* [ndir][B] relative residual of the scaled system, as mpcqp_adjoint's */
+  int8_t *act;         /* [B][m] as mpcqp_adjoint's */
+  int32_t *status_tangent; /* [B] 1 done, 0 not attempted */
+} mpcqp_tangent_out;
+int mpcqp_tangent(mpcqp_handle *h, const int32_t *status, const double *x, const double *y,
+                  const mpcqp_tangent_in *in, const mpcqp_tangent_out *out);
 
 /* Zero-copy access to the handle's own problem-data buffers (device): Ax [B*nnzA], l, u [B*m].
  * A producer kernel (e.g. mpcqp_cl_configure) may rewrite them in place between solves, on the

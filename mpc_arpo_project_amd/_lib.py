@@ -53,7 +53,7 @@ EXPORTED = (
     "mpcqp_update_P_batched", "mpcqp_cl_set_id_period",
     "mpcqp_check_settings", "mpcqp_set_settings_batched", "mpcqp_update_settings",
     "mpcqp_update_settings_batched", "mpcqp_update_rho", "mpcqp_update_rho_batched",
-    "mpcqp_get_settings", "mpcqp_polish", "mpcqp_adjoint",
+    "mpcqp_get_settings", "mpcqp_polish", "mpcqp_adjoint", "mpcqp_tangent",
     "mpcqp_cl_create", "mpcqp_cl_destroy", "mpcqp_cl_configure", "mpcqp_cl_step",
     "mpcqp_cl_set_ids", "mpcqp_cl_set_tracking", "mpcqp_cl_noise", "mpcqp_cl_set_plant", "mpcqp_clc_period",
     "mpcqp_clc_set_tracking",
@@ -66,6 +66,7 @@ PREDATED = (
     "mpcqp_get_scaling", "mpcqp_check_settings", "mpcqp_set_settings_batched",
     "mpcqp_update_settings", "mpcqp_update_settings_batched", "mpcqp_update_rho",
     "mpcqp_update_rho_batched", "mpcqp_get_settings", "mpcqp_polish", "mpcqp_adjoint",
+    "mpcqp_tangent",
 )
 
 STATUS = {
@@ -118,6 +119,16 @@ class AdjointOut(C.Structure):
     _fields_ = [("gq", C.c_void_p), ("gl", C.c_void_p), ("gu", C.c_void_p), ("gPx", C.c_void_p),
                 ("gAx", C.c_void_p), ("res", C.c_void_p), ("act", C.c_void_p),
                 ("status_adjoint", C.c_void_p)]
+
+
+class TangentIn(C.Structure):
+    _fields_ = [("ndir", C.c_int32), ("refine", C.c_int32), ("dq", C.c_void_p), ("dl", C.c_void_p),
+                ("du", C.c_void_p), ("dAx", C.c_void_p), ("dPx", C.c_void_p)]
+
+
+class TangentOut(C.Structure):
+    _fields_ = [("dx", C.c_void_p), ("dy", C.c_void_p), ("dz", C.c_void_p), ("dobj", C.c_void_p),
+                ("res", C.c_void_p), ("act", C.c_void_p), ("status_tangent", C.c_void_p)]
 
 
 class ClScenario(C.Structure):
@@ -200,6 +211,7 @@ def lib():
     _sig(L, "mpcqp_solve", "argtypes", [vp, dp, dp, C.POINTER(Info)])
     _sig(L, "mpcqp_polish", "argtypes", [vp, dp, dp, dp, C.POINTER(PolishInfo)])
     _sig(L, "mpcqp_adjoint", "argtypes", [vp, dp, dp, dp, C.POINTER(AdjointIn), C.POINTER(AdjointOut)])
+    _sig(L, "mpcqp_tangent", "argtypes", [vp, dp, dp, dp, C.POINTER(TangentIn), C.POINTER(TangentOut)])
     _sig(L, "mpcqp_dims", "argtypes", [vp, i32p, i32p, i32p, i32p, i32p])
     _sig(L, "mpcqp_engine_kind", "argtypes", [vp, i32p])
     _sig(L, "mpcqp_schedule_kind", "argtypes", [vp, i32p])

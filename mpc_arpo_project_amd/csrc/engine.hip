@@ -2491,6 +2491,7 @@ constexpr int PAIR_PIPE = MPCQP_PAIR_PIPE;
 #include "engine_pair.inc"
 #include "engine_polish.inc"
 #include "engine_adjoint.inc"
+#include "engine_tangent.inc"
 
 // dst[b][k] = src[k] for every instance b (the drift buffers' start: set_data, update_lin_cost)
 __global__ void bcast_rows_kernel(double* dst, const double* src, int B, int cnt) {
@@ -2674,6 +2675,11 @@ struct mpcqp_handle {
   adjoint_fn akern = nullptr;
   int agrid = 0;
   double* ascratch = nullptr;
+  // forward sensitivities (mpcqp_tangent): valid where the adjoint is (adjoint_ok); the kernel, its
+  // grid and its scratch rows, set up at the first call
+  tangent_fn tkern = nullptr;
+  int tgrid = 0;
+  double* tscratch = nullptr;
 };
 
 // device memory owned by the handle: recorded, and freed by mpcqp_destroy
@@ -3236,6 +3242,63 @@ int mpcqp_adjoint(mpcqp_handle* h, const int32_t* status, const double* x, const
   ap.status = status, ap.x = x, ap.y = y;
   ap.in = *in, ap.out = *out;
   hipLaunchKernelGGL(h->akern, dim3(h->agrid), dim3(64), h->dp.inst_doubles * 8, h->stream, ap);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// The tangent kernel of the handle's plan, its persistent grid and a scratch row per wave (the
+// polish's row), as adjoint_setup: at the first mpcqp_tangent
+static int tangent_setup(mpcqp_handle* h) {
+  const Plan& pl = h->plan;
+  const tangent_fn k = select_tangent(pl.n, pl.m, pl.paired);
+  if (!k) return set_error(MPCQP_E_UNSUPPORTED, "mpcqp_tangent: problem dimensions exceed the instantiated kernels");
+  int dev = 0, ncu = 0, nb = 0;
+  HIPCHK(hipGetDevice(&dev));
+  HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+  HIPCHK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  hipFuncAttributes fa{};
+  HIPCHK(hipFuncGetAttributes(&fa, (const void*)k));
+  if (fa.numRegs > diag_env_int("MPCQP_REG_BUDGET", MPCQP_MAX_KERNEL_REGS) ||
+      (int)fa.localSizeBytes > MPCQP_MAX_KERNEL_SCRATCH)
+    return set_error(MPCQP_E_UNSUPPORTED,
+                     "mpcqp_tangent: tangent kernel allocates " + std::to_string(fa.numRegs) + " registers / " +
+                         std::to_string(fa.localSizeBytes) + " scratch bytes per lane: above the validated budget");
+  const int lds = h->dp.inst_doubles * 8;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k, 64, lds) != hipSuccess || nb <= 0)
+    return set_error(MPCQP_E_UNSUPPORTED, "mpcqp_tangent: kernel does not fit on a CU (LDS/VGPR)");
+  const int grid = std::min(h->B, nb * ncu);
+  if (!dev_alloc(h, h->tscratch,
+                 sizeof(double) * (size_t)grid * polish_row_doubles(pl.n, pl.m, pl.mv_slab, pl.nnzP)))
+    return set_error(MPCQP_E_HIP, "mpcqp_tangent: hipMalloc(scratch rows)");
+  h->tgrid = grid;
+  h->tkern = k;
+  return 0;
+}
+
+int mpcqp_tangent(mpcqp_handle* h, const int32_t* status, const double* x, const double* y,
+                  const mpcqp_tangent_in* in, const mpcqp_tangent_out* out) {
+  if (!h) return set_error(MPCQP_E_INVALID, "mpcqp_tangent: null handle");
+  if (!status || !x || !y || !in || !out) return set_error(MPCQP_E_INVALID, "mpcqp_tangent: null argument");
+  if (in->ndir < 1 || in->ndir > 8)
+    return set_error(MPCQP_E_INVALID, "mpcqp_tangent: ndir must be 1..8, got " + std::to_string(in->ndir));
+  if (in->refine < 0)
+    return set_error(MPCQP_E_INVALID, "mpcqp_tangent: refine must not be negative");
+  if (!in->dq && !in->dl && !in->du && !in->dAx && !in->dPx)
+    return set_error(MPCQP_E_INVALID, "mpcqp_tangent: no perturbation given (dq, dl, du, dAx, dPx are all null)");
+  if (!h->adjoint_ok)
+    return set_error(MPCQP_E_INVALID,
+                     "mpcqp_tangent: the handle's carried state is not that of its last solve");
+  for (size_t i = 0; i < std::max<size_t>(h->rows.size(), 1); ++i)
+    if (!((h->rows.empty() ? h->set : h->rows[i]).delta > 0))
+      return set_error(MPCQP_E_INVALID, "mpcqp_tangent: row " + std::to_string(i) + ": delta must be positive");
+  if (!h->tkern)
+    if (int rc = tangent_setup(h)) return rc;
+  TParams tp{};
+  tp.k = kernel_params(h, nullptr, nullptr);
+  tp.k.scratch = h->tscratch;
+  tp.status = status, tp.x = x, tp.y = y;
+  tp.in = *in, tp.out = *out;
+  hipLaunchKernelGGL(h->tkern, dim3(h->tgrid), dim3(64), h->dp.inst_doubles * 8, h->stream, tp);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -4,6 +4,9 @@
 unscaled x [B, n] and y [B, m]; torch.autograd carries a loss on them back to the data through one
 adjoint launch (BatchQP.adjoint, mpcqp_adjoint): the one-sided derivative on the solution's active
 set, as in every QP layer.  Instances the solve did not solve contribute zero gradients.
+torch.autograd.forward_ad carries tangents of the data forward through the solve instead, by one
+tangent launch right behind it (BatchQP.tangent, mpcqp_tangent): the mode for a closed loop, where
+the handle moves on before a backward pass could come back to a step.
 
 The backward contract: q, l, u, Ax, Px are per instance ([B, .]); a shared 1-D q or Px receives
 the sum over the batch.  One backward per forward: the adjoint reads the state the handle carries,
@@ -33,6 +36,16 @@ class _QPSolve(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         # the handle's output buffers are overwritten by its next solve: hand out copies
         return r.x.clone(), r.y.clone()
+
+    @staticmethod
+    def jvp(ctx, _qp, _polish, *tangents):
+        # forward mode (torch.autograd.forward_ad): called right behind forward, while the handle
+        # carries its state -- one tangent launch, one direction; a shared 1-D tangent is every
+        # instance's
+        qp = ctx.qp
+        d = [None if t is None else t.expand(qp.B, -1) if t.dim() == 1 else t for t in tangents]
+        t = qp.tangent(*d[:3], dAx=d[3], dPx=d[4], out=ctx.result)
+        return t.dx[0], t.dy[0]
 
     @staticmethod
     def backward(ctx, gx, gy):

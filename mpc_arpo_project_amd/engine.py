@@ -86,6 +86,19 @@ class AdjointResult:
     status_adjoint: torch.Tensor  # [B] int32: 1 done, 0 not attempted
 
 
+@dataclass
+class TangentResult:
+    """Outputs of BatchQP.tangent, [ndir, B, .]; None where not requested.  Rows of instances that
+    were not attempted (status_tangent 0) are zero."""
+    dx: torch.Tensor             # [ndir, B, n]
+    dy: torch.Tensor             # [ndir, B, m], 0 off the active rows
+    dz: torch.Tensor             # [ndir, B, m] d(Ax) = A dx + dA x
+    dobj: torch.Tensor           # [ndir, B] d(x'Px/2 + q'x)
+    res: torch.Tensor            # [ndir, B] relative residual of the scaled system
+    act: torch.Tensor            # [B, m] int8: -1 lower-active, +1 upper-active, 0 inactive
+    status_tangent: torch.Tensor  # [B] int32: 1 done, 0 not attempted
+
+
 class BatchQP:
     """B OSQP problems with a shared pattern, solved together on one GPU."""
 
@@ -483,6 +496,65 @@ class BatchQP:
         check(_lib.lib().mpcqp_adjoint(self._h, st.data_ptr(), o.x.data_ptr(), o.y.data_ptr(),
                                        C.byref(ain), C.byref(aout)), "mpcqp_adjoint")
         for t in (gx, gy):
+            if t is not None:
+                t.record_stream(self.stream)
+        if sync:
+            self.stream.synchronize()
+        else:
+            torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        return r
+
+    TANGENT_OUTPUTS = ("dx", "dy", "dz", "dobj")
+
+    def tangent(self, dq=None, dl=None, du=None, dAx=None, dPx=None, refine=3, status=None,
+                want=("dx", "dy"), out: SolveResult = None, sync=True) -> TangentResult:
+        """Forward sensitivities of the instances the last solve solved (mpcqp_tangent): the
+        perturbations dq [ndir, B, n], dl, du [ndir, B, m], dAx [ndir, B, nnzA], dPx [ndir, B, nnzP]
+        (2-D: ndir = 1; None: zero; at least one given, all with the same ndir <= 8) give the
+        tangents named in `want` (of dx, dy, dz, dobj), [ndir, B, .], with one factorization per
+        instance for all directions and `refine` rounds of iterative refinement each.  out, status,
+        the validity and the streams are BatchQP.adjoint's; changes no state."""
+        o = out if out is not None else getattr(self, "_last", None)
+        if o is None:
+            raise MPCQPError("mpcqp_tangent: tangent before any solve")
+        st = o.status if status is None else status
+        if st.dtype != torch.int32 or tuple(st.shape) != (self.B,) or not st.is_cuda or \
+                not st.is_contiguous():
+            raise ValueError(f"status must be a contiguous int32 device tensor of shape ({self.B},)")
+        unknown = [w for w in want if w not in self.TANGENT_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown tangent outputs {unknown}: choose from {self.TANGENT_OUTPUTS}")
+        width = dict(dq=self.n, dl=self.m, du=self.m, dAx=self.nnzA, dPx=self.nnzP)
+        d, ndir = {}, None
+        for k, t in dict(dq=dq, dl=dl, du=du, dAx=dAx, dPx=dPx).items():
+            if t is None:
+                d[k] = None
+                continue
+            t = torch.as_tensor(t, dtype=torch.float64, device=self.device)
+            t = t.unsqueeze(0) if t.dim() == 2 else t
+            ndir = int(t.shape[0]) if ndir is None else ndir
+            if t.dim() != 3 or tuple(t.shape) != (ndir, self.B, width[k]):
+                raise ValueError(f"{k} must have shape ({ndir or 'ndir'}, {self.B}, {width[k]}) or "
+                                 f"({self.B}, {width[k]})")
+            d[k] = t.contiguous()
+        if ndir is None:
+            raise MPCQPError("mpcqp_tangent: no perturbation given")
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))  # the inputs are complete
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            f = dict(dtype=torch.float64, device=self.device)
+            shape = dict(dx=(self.n,), dy=(self.m,), dz=(self.m,), dobj=())
+            g = {k: torch.empty(ndir, self.B, *shape[k], **f) if k in want else None
+                 for k in self.TANGENT_OUTPUTS}
+            r = TangentResult(**g, res=torch.empty(ndir, self.B, **f),
+                              act=torch.empty(self.B, self.m, dtype=torch.int8, device=self.device),
+                              status_tangent=torch.empty(self.B, dtype=torch.int32, device=self.device))
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        tin = _lib.TangentIn(ndir, int(refine), *(ptr(d[k]) for k in ("dq", "dl", "du", "dAx", "dPx")))
+        tout = _lib.TangentOut(*(ptr(g[k]) for k in self.TANGENT_OUTPUTS), r.res.data_ptr(),
+                               r.act.data_ptr(), r.status_tangent.data_ptr())
+        check(_lib.lib().mpcqp_tangent(self._h, st.data_ptr(), o.x.data_ptr(), o.y.data_ptr(),
+                                       C.byref(tin), C.byref(tout)), "mpcqp_tangent")
+        for t in d.values():
             if t is not None:
                 t.record_stream(self.stream)
         if sync:

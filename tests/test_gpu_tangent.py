@@ -1,0 +1,153 @@
+"""mpcqp_tangent: forward sensitivities against a numpy.longdouble reference on the engine's reported
+active sets, their duality with mpcqp_adjoint, the call contract, and forward_ad through
+diff.qp_solve.
+
+The reference is the adjoint test's (test_gpu_adjoint.Ref: the dense unscaled reduced KKT,
+equilibrated symmetrically in longdouble) with the right-hand side assembled in longdouble from the
+perturbations; the floor is the plain float64 LAPACK solve of the same system and the engine gets
+MARGIN = 10 times the case's worst floor -- same matrix, same refinement, same rule.  An error is
+the max-norm over an instance's [ndir, .] output relative to the reference's max-norm of it."""
+import numpy as np
+import pytest
+import scipy.sparse as sp
+import torch
+import torch.autograd.forward_ad as fwad
+
+from mpc_arpo_project_amd import _lib, diff
+from mpc_arpo_project_amd._lib import MPCQPError
+from mpc_arpo_project_amd.engine import BatchQP
+from test_gpu_adjoint import MARGIN, L, Ref, _err, _np, _random_qp
+
+pytestmark = pytest.mark.gpu
+OUTS = ("dx", "dy", "dz", "dobj")
+WIDTH = dict(dq="n", dl="m", du="m", dAx="nnzA", dPx="nnzP")
+
+
+def _perturb(rng, qp, ndir, B, names=tuple(WIDTH)):
+    return {k: rng.standard_normal((ndir, B, getattr(qp, WIDTH[k]))) for k in names}
+
+
+def _reference(qp, q, Ax, act, x, y, pert):
+    """one instance: pert[k] [ndir, .] -> (Ref, longdouble outputs, plain float64 outputs)"""
+    ref, n, m = Ref(qp, Ax, act), qp.n, qp.m
+    ndir = len(next(iter(pert.values())))
+    dq, dl, du, dA, dP = (pert.get(k, np.zeros((ndir, getattr(qp, w)))).astype(L) for k, w in WIDTH.items())
+    dense = lambda M, data: sp.csc_matrix((data.astype(float), M.indices, M.indptr), shape=M.shape).toarray()  # noqa: E731
+    Pu, A = qp.P.toarray(), dense(qp.A, Ax)
+    Pf = Pu + np.triu(Pu, 1).T
+    dAd = [dense(qp.A, dA[k]).astype(L) for k in range(ndir)]
+    dPd = [(lambda U: U + np.triu(U, 1).T)(dense(qp.P, dP[k])).astype(L) for k in range(ndir)]
+    xl, ya = x.astype(L), np.where(act != 0, y, 0).astype(L)
+    rx = np.array([-(dq[k] + dPd[k] @ xl + dAd[k].T @ ya) for k in range(ndir)])
+    ry = np.array([np.where(act < 0, dl[k], np.where(act > 0, du[k], 0)) - dAd[k] @ xl for k in range(ndir)])
+
+    def outs(d, T):
+        xt, o = x.astype(T), {k: [] for k in OUTS}
+        for k in range(ndir):
+            dx, dy = d[:n, k].astype(T), np.zeros(m, dtype=T)
+            dy[ref.rows] = d[n:, k]
+            o["dx"].append(dx), o["dy"].append(dy)
+            o["dz"].append(A.astype(T) @ dx + dAd[k].astype(T) @ xt)
+            o["dobj"].append(.5 * xt @ dPd[k].astype(T) @ xt + dq[k].astype(T) @ xt + (Pf.astype(T) @ xt + q.astype(T)) @ dx)
+        return {k: np.array(a) for k, a in o.items()}
+
+    d, d64 = ref.solve(ref.rhs(rx, ry))
+    return ref, outs(d, L), outs(d64, float)
+
+
+@pytest.mark.parametrize("paired", ["1", "0"])
+@pytest.mark.parametrize("seed", [1, 10])
+def test_random_structures_against_longdouble_and_adjoint(monkeypatch, seed, paired):
+    monkeypatch.setenv("MPCQP_DIAGNOSTICS", "1")
+    monkeypatch.setenv("MPCQP_PAIRED", paired)
+    B, rng = 16, np.random.default_rng(seed)
+    P, q, A, Ax, l, u = _random_qp(seed, B)
+    qp = BatchQP(P, A, batch=B, eps_abs=1e-6, eps_rel=1e-6)
+    qp.set_data(q=q, Ax=Ax, l=l, u=u)
+    status = qp.solve().status.cpu().numpy()
+    pol = _np(qp.polish(), ("status_polish", "x", "y"))
+    full = _perturb(rng, qp, 3, B)
+    names = OUTS + ("res", "act", "status_tangent")
+    runs = [(p, _np(qp.tangent(**p, refine=5, want=OUTS), names))
+            for p in (full, {k: full[k] for k in ("dl", "du")})]
+    assert np.array_equal(runs[0][1]["status_tangent"], (status == 1).astype(np.int32))
+    # duality: <g, K^-1 r(p)> by the tangent of p and by the adjoint of g, direction 0 of `full`
+    gx, gy = rng.standard_normal((B, qp.n)), rng.standard_normal((B, qp.m))
+    adj = _np(qp.adjoint(gx, gy, refine=5, want=("gq", "gl", "gu", "gAx", "gPx")), ("gq", "gl", "gu", "gAx", "gPx"))
+    e0 = runs[0][1]
+    fwd = [gx * e0["dx"][0], gy * e0["dy"][0]]
+    rev = [adj["g" + k[1:]][0] * full[k][0] for k in WIDTH]
+    floor, worst, res, dual, counted = 0.0, 0.0, 0.0, 0.0, 0
+    for b in np.flatnonzero(status == 1):
+        for p, e in runs:
+            ref, want, plain = _reference(qp, q, Ax[b], e["act"][b], pol["x"][b], pol["y"][b], {k: a[:, b] for k, a in p.items()})
+            if pol["status_polish"][b] != 1 or ref.cond > 1e5:
+                break
+            floor = max([floor] + [_err(plain[o], want[o]) for o in OUTS])
+            worst = max([worst] + [_err(e[o][:, b], want[o]) for o in OUTS])
+            res = max(res, e["res"][:, b].max())
+        else:
+            counted += 1
+            lhs, rhs = sum(t[b].sum() for t in fwd), sum(t[b].sum() for t in rev)
+            dual = max(dual, abs(lhs - rhs) / sum(np.abs(t[b]).sum() for t in fwd + rev))
+    print(f"seed {seed} paired {paired}: counted {counted}, fp64 floor {floor:.2e}, engine {worst:.2e}, "
+          f"res {res:.2e}, duality {dual:.2e}")
+    assert counted >= 15
+    assert worst <= MARGIN * floor and res <= MARGIN * floor and dual <= MARGIN * floor
+
+
+def test_tangent_contract(golden, prob20):
+    d, B = golden("batch_n20"), 16
+    data = dict(q=prob20.q, Ax=d["Ax"][:B], l=d["l"][:B], u=d["u"][:B])
+    qp = BatchQP(prob20.P, prob20.A, batch=B, eps_abs=1e-6, eps_rel=1e-6)
+    qp.set_data(**data)
+    r = qp.solve()
+    p = _perturb(np.random.default_rng(0), qp, 2, B)
+    names = OUTS + ("res", "act", "status_tangent")
+    a0, a1 = (_np(qp.tangent(**p, want=OUTS), names) for _ in range(2))
+    assert all(np.array_equal(a0[k], a1[k]) for k in names) and a0["dx"].any()  # repeatable bitwise
+    forced, skip = r.status.clone(), torch.zeros(B, dtype=torch.int32, device="cuda")
+    solved = np.flatnonzero(r.status.cpu().numpy() == 1)
+    forced[solved[0]], skip[solved[1]] = -2, 1
+    qp.set_skip(skip)
+    z = _np(qp.tangent(**p, status=forced, want=OUTS), names)
+    qp.set_skip(None)
+    for b in solved[:2]:  # not attempted: zeros in every row
+        assert z["status_tangent"][b] == 0 and not z["act"][b].any()
+        assert not any(z[k][:, b].any() for k in OUTS + ("res",))
+    assert np.array_equal(z["dx"][:, solved[2:]], a0["dx"][:, solved[2:]])
+    assert (_np(qp.polish(), ("status_polish",))["status_polish"] != 0).any()  # solve -> tangent -> polish
+    assert (_np(qp.tangent(dl=p["dl"]), ("status_tangent",))["status_tangent"] == 1).any()
+    for bad in (np.zeros((0, B, qp.m)), np.zeros((9, B, qp.m))):
+        with pytest.raises(MPCQPError, match=r"\(-1\): mpcqp_tangent: ndir"):
+            qp.tangent(dl=bad)
+    rc = _lib.lib().mpcqp_tangent(qp._h, r.status.data_ptr(), r.x.data_ptr(), r.y.data_ptr(),
+                                  _lib.C.byref(_lib.TangentIn(1, 3)), _lib.C.byref(_lib.TangentOut()))
+    assert rc == -1 and _lib.lib().mpcqp_last_error().decode().startswith("mpcqp_tangent: no perturbation")
+    qp.update(l=data["l"], u=data["u"])
+    with pytest.raises(MPCQPError, match=r"\(-1\): mpcqp_tangent"):
+        qp.tangent(dl=p["dl"])
+
+
+def test_forward_ad_through_qp_solve():
+    B, f, rng = 4, dict(dtype=torch.float64, device="cuda"), np.random.default_rng(3)
+    P, q, A, Ax, l, u = _random_qp(1, B)
+    qp = BatchQP(P, A, batch=B, eps_abs=1e-6, eps_rel=1e-6)
+    p = _perturb(rng, qp, 1, B, ("dq", "dl", "du", "dAx"))
+    prim = dict(dq=np.broadcast_to(q, (B, qp.n)).copy(), dl=l, du=u, dAx=Ax)
+    with fwad.dual_level():
+        duals = [fwad.make_dual(torch.tensor(prim[k], **f), torch.tensor(p[k][0], **f)) for k in p]
+        x, y = diff.qp_solve(qp, *duals[:3], Ax=duals[3])
+        (xs, dx), (ys, dy) = ([t.cpu().numpy() for t in fwad.unpack_dual(o)] for o in (x, y))
+    t = _np(qp.tangent(**p), ("dx", "dy", "act", "status_tangent"))
+    assert np.array_equal(dx, t["dx"][0]) and np.array_equal(dy, t["dy"][0]) and dx.any()
+    floor, worst, counted = 0.0, 0.0, 0
+    for b in np.flatnonzero(t["status_tangent"] == 1):
+        ref, want, plain = _reference(qp, q, Ax[b], t["act"][b], xs[b], ys[b], {k: a[:, b] for k, a in p.items()})
+        if ref.cond > 1e5:
+            continue
+        counted += 1
+        floor = max([floor] + [_err(plain[o], want[o]) for o in ("dx", "dy")])
+        worst = max(worst, _err(dx[b], want["dx"][0]), _err(dy[b], want["dy"][0]))
+    print(f"forward_ad: counted {counted}, fp64 floor {floor:.2e}, engine {worst:.2e}")
+    assert counted >= 3 and worst <= MARGIN * floor
