@@ -2870,6 +2870,11 @@ int mpcqp_create(const mpcqp_structure* st, const mpcqp_settings* s, int32_t bat
   if (hipMemset(h->has_state, 0, I * Bz) != hipSuccess || hipMemsetD32(h->dsel, -2, Bz) != hipSuccess ||
       hipMemset(h->pend, 0, I * Bz) != hipSuccess)
     return fail(MPCQP_E_HIP, "hipMemset");
+  // the carried iterates of an instance no solve has reached yet (skipped from the first solve on)
+  // are defined: mpcqp_get_state reports zeros for it, not what the allocation happened to hold
+  if (hipMemset(h->xs, 0, D * Bz * pl.n) != hipSuccess || hipMemset(h->zs, 0, D * Bz * pl.m) != hipSuccess ||
+      hipMemset(h->ys, 0, D * Bz * pl.m) != hipSuccess)
+    return fail(MPCQP_E_HIP, "hipMemset");
   *out = h;
   return 0;
 }

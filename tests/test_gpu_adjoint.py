@@ -6,6 +6,8 @@ The reference: the dense unscaled reduced KKT [[P, A_act'], [A_act, 0]], equilib
 in longdouble (the same linear system), solved by float64 LU with longdouble iterative refinement to
 a longdouble residual; the first, unrefined float64 solve is the floor a plain fp64 solver reaches
 and the engine gets MARGIN = 10 times the case's worst floor (Adjoint solves: measured)."""
+import functools
+
 import numpy as np
 import pytest
 import scipy.linalg as sla
@@ -51,9 +53,9 @@ def _random_qp(seed, B):  # tests/test_gpu_random_structures.py::_random_qp
 class Ref:
     """the reduced KKT of one instance on the active rows `act`, equilibrated in longdouble"""
 
-    def __init__(self, qp, Ax, act):
+    def __init__(self, qp, Ax, act, Px=None):  # Px: the instance's own P values (default: qp.P's)
         self.qp, self.rows, n = qp, np.flatnonzero(act), qp.n
-        Pu = qp.P.toarray()
+        Pu = qp.P.toarray() if Px is None else sp.csc_matrix((Px, qp.P.indices, qp.P.indptr), shape=qp.P.shape).toarray()
         Pf = Pu + np.triu(Pu, 1).T
         Ar = sp.csc_matrix((Ax, qp.A.indices, qp.A.indptr), shape=qp.A.shape).toarray()[self.rows]
         k = len(self.rows)
@@ -63,7 +65,18 @@ class Ref:
             nrm = np.max(np.abs(self.K * np.outer(self.s, self.s)), axis=1)
             self.s /= np.sqrt(np.where(nrm > 0, nrm, 1))
         self.Ke = self.K * np.outer(self.s, self.s)
-        self.cond, self.cond_eq = np.linalg.cond(self.K.astype(float)), np.linalg.cond(self.Ke.astype(float))
+
+    @functools.cached_property
+    def cond(self):
+        return np.linalg.cond(self.K.astype(float))
+
+    @functools.cached_property
+    def cond_eq(self):
+        return np.linalg.cond(self.Ke.astype(float))
+
+    @functools.cached_property
+    def lu(self):
+        return sla.lu_factor(self.Ke.astype(float))
 
     def rhs(self, gx, gy):  # [nrhs, n], [nrhs, m] or None -> equilibrated right-hand sides, columns
         gy = np.zeros((len(gx), self.qp.m)) if gy is None else gy
@@ -71,7 +84,7 @@ class Ref:
 
     def solve(self, be):
         """(longdouble solution, plain float64 solution) of the unscaled system, columns"""
-        lu = sla.lu_factor(self.Ke.astype(float))
+        lu = self.lu
         d64 = sla.lu_solve(lu, be.astype(float))
         d = d64.astype(L)
         for _ in range(6):
@@ -155,23 +168,19 @@ def test_random_structures_against_longdouble(monkeypatch, seed, paired):
 RES_MULT = 100.0
 
 
-@pytest.mark.parametrize("tag,Nx,dv", [("batch_n20", 20, False), ("batch_n40dv", 40, True)])
-def test_mpc_residual_and_gain(golden, tag, Nx, dv):
-    from conftest import problem
-
-    prob, d, B = problem(Nx, dv), golden(tag), 16
-    qp = BatchQP(prob.P, prob.A, batch=B, eps_abs=1e-6, eps_rel=1e-6, polish_refine_iter=20, max_iter=20000)
-    qp.set_data(q=prob.q, Ax=d["Ax"][:B], l=d["l"][:B], u=d["u"][:B])
-    r = qp.solve()
+def mpc_residual_and_gain(qp, prob, Ax, status, tag):
+    """test_mpc_residual_and_gain's assertions on the state qp carries after its last solve (status:
+    that solve's, numpy; Ax: the data it solved, [B, nnzA]); returns the number of qualified instances"""
+    B = qp.B
     pol = _np(qp.polish(), ("status_polish", "x", "y"))
     gx = np.zeros((prob.nu, B, qp.n))
     for k in range(prob.nu):
         gx[k, :, prob.u0_slice.start + k] = 1.0
     e = _np(qp.adjoint(gx, refine=20), ("gq", "gl", "gu", "res", "act", "status_adjoint"))
-    assert np.array_equal(e["status_adjoint"] == 1, r.status.cpu().numpy() == 1)
+    assert np.array_equal(e["status_adjoint"] == 1, status == 1)
     qualified = 0
     for b in np.flatnonzero(e["status_adjoint"] == 1):
-        ref = Ref(qp, d["Ax"][b], e["act"][b])
+        ref = Ref(qp, Ax[b], e["act"][b])
         be = ref.rhs(gx[:, b], None)
         de = np.hstack([-e["gq"][:, b], (e["gl"] + e["gu"])[:, b][:, ref.rows]]).astype(L)
         true = ref.residual(de, be)
@@ -192,7 +201,18 @@ def test_mpc_residual_and_gain(golden, tag, Nx, dv):
         floor, err = (float(np.max(np.abs(g - gain))) / scale for g in (g64, geng))
         print(f"{tag} {b}: gain max {float(np.max(np.abs(gain))):.2e} of {float(big):.2e}, floor {floor:.2e} engine {err:.2e}")
         assert err <= MARGIN * max(floor, 2.0 ** -52), b
-    assert qualified >= 5
+    return qualified
+
+
+@pytest.mark.parametrize("tag,Nx,dv", [("batch_n20", 20, False), ("batch_n40dv", 40, True)])
+def test_mpc_residual_and_gain(golden, tag, Nx, dv):
+    from conftest import problem
+
+    prob, d, B = problem(Nx, dv), golden(tag), 16
+    qp = BatchQP(prob.P, prob.A, batch=B, eps_abs=1e-6, eps_rel=1e-6, polish_refine_iter=20, max_iter=20000)
+    qp.set_data(q=prob.q, Ax=d["Ax"][:B], l=d["l"][:B], u=d["u"][:B])
+    r = qp.solve()
+    assert mpc_residual_and_gain(qp, prob, d["Ax"][:B], r.status.cpu().numpy(), tag) >= 5
 
 
 @pytest.mark.parametrize("case", ["update_bounds", "warm_start", "set_data", "nrhs0", "nrhs9", "delta", "stable"])

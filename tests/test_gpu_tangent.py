@@ -27,13 +27,14 @@ def _perturb(rng, qp, ndir, B, names=tuple(WIDTH)):
     return {k: rng.standard_normal((ndir, B, getattr(qp, WIDTH[k]))) for k in names}
 
 
-def _reference(qp, q, Ax, act, x, y, pert):
-    """one instance: pert[k] [ndir, .] -> (Ref, longdouble outputs, plain float64 outputs)"""
-    ref, n, m = Ref(qp, Ax, act), qp.n, qp.m
+def _reference(qp, q, Ax, act, x, y, pert, Px=None, ref=None):
+    """one instance: pert[k] [ndir, .] -> (Ref, longdouble outputs, plain float64 outputs); Px: the
+    instance's own P values (default: qp.P's); ref: the Ref of (Ax, act, Px), if the caller has it"""
+    ref, n, m = ref or Ref(qp, Ax, act, Px), qp.n, qp.m
     ndir = len(next(iter(pert.values())))
     dq, dl, du, dA, dP = (pert.get(k, np.zeros((ndir, getattr(qp, w)))).astype(L) for k, w in WIDTH.items())
     dense = lambda M, data: sp.csc_matrix((data.astype(float), M.indices, M.indptr), shape=M.shape).toarray()  # noqa: E731
-    Pu, A = qp.P.toarray(), dense(qp.A, Ax)
+    Pu, A = qp.P.toarray() if Px is None else dense(qp.P, Px), dense(qp.A, Ax)
     Pf = Pu + np.triu(Pu, 1).T
     dAd = [dense(qp.A, dA[k]).astype(L) for k in range(ndir)]
     dPd = [(lambda U: U + np.triu(U, 1).T)(dense(qp.P, dP[k])).astype(L) for k in range(ndir)]
