@@ -24,6 +24,7 @@
  *   mpcqp_polish                   <- the polish step of osqp_solve under settings.polish  [polish]
  *   mpcqp_adjoint                  <- no OSQP call: the adjoint solve of a differentiable QP layer
  *   mpcqp_tangent                  <- no OSQP call: its forward-mode counterpart (tangents)
+ *   mpcqp_adjoint_tape / _replay   <- no OSQP call: the adjoint of an earlier solve, from a record
  *   mpcqp_update_settings          <- prob.update_settings(max_iter=, eps_abs=, ...)
  *                                     [osqp_update_max_iter, osqp_update_eps_abs, ...]
  *   mpcqp_update_rho               <- prob.update_settings(rho=)  [osqp_update_rho]
@@ -308,6 +309,49 @@ typedef struct {       /* device, any may be NULL */
 } mpcqp_tangent_out;
 int mpcqp_tangent(mpcqp_handle *h, const int32_t *status, const double *x, const double *y,
                   const mpcqp_tangent_in *in, const mpcqp_tangent_out *out);
+
+/* Adjoint tape and replay: reverse-mode gradients through many solves of one handle (a rollout, a
+ * closed-loop objective) with one backward sweep at the end.  mpcqp_adjoint reads the state the
+ * handle carries and is gone with the handle's next data call; a TAPE records, right after a solve,
+ * the part of that state the adjoint needs and cannot get back -- the active rows -- and the caller
+ * keeps the data and the solution of that solve.  mpcqp_adjoint_replay then does the adjoint solve
+ * from the record alone, with the handle in any state.
+ *
+ * mpcqp_adjoint_tape: legal exactly where mpcqp_adjoint is (after a solve or a polish of it;
+ * MPCQP_E_INVALID otherwise).  status as mpcqp_adjoint's.  Writes act [B][m] (-1 lower-active, +1
+ * upper-active, 0 inactive) and taped [B] (1 where mpcqp_adjoint would attempt the instance, 0
+ * elsewhere, with a zero act row): bit for bit what mpcqp_adjoint called at the same point writes to
+ * act and status_adjoint.  One elementwise launch over the carried iterates; changes no handle
+ * state; asynchronous on the handle's stream.  Every error message starts with
+ * "mpcqp_adjoint_tape".
+ *
+ * mpcqp_adjoint_replay: in / out are mpcqp_adjoint's and keep their meaning; out.act echoes
+ * pt->act, instances with taped == 0 get zero rows and status_adjoint = 0.  The handle serves as
+ * the compiled plan and factorization program, the settings rows (delta, the Ruiz pass count), the
+ * scratch memory and the stream, nothing else: the call reads and writes no carried state, so it is
+ * legal in every handle state after mpcqp_create (before mpcqp_set_data too, and after any later
+ * solve or update), it may be repeated (bitwise the same outputs), and a following mpcqp_polish,
+ * mpcqp_adjoint or mpcqp_tangent is as legal as before with unchanged results.  Every array of
+ * the point must stay unchanged until the call has run on the stream.
+ * The taped data are equilibrated from scratch (OSQP's scale_data on Px, q, Ax, l, u as given).
+ * mpcqp_adjoint redoes the handle's own last scaling, which after updates of A started from the
+ * drifted P, q OSQP carries; so a replay equals mpcqp_adjoint at the same point to rounding, and bit
+ * for bit where that scaling started from the set-up data (e.g. the first solve after
+ * mpcqp_set_data[_batched]) and Px, q are the set-up values.
+ * Errors: a missing required pointer, nrhs outside 1..8, refine < 0 or a settings row with
+ * delta <= 0 are MPCQP_E_INVALID; the kernel's register / scratch budget is checked at the first
+ * call as in mpcqp_adjoint.  Every error message starts with "mpcqp_adjoint_replay". */
+typedef struct {
+  const double *Px, *q;   /* device; shared [nnzP]/[n] or per instance [B*nnzP]/[B*n] */
+  int32_t Px_batched, q_batched;
+  const double *Ax, *l, *u;   /* device [B*nnzA], [B*m], [B*m]: the data of the taped solve */
+  const double *x, *y;        /* device [B*n], [B*m]: the unscaled solution at the tape point */
+  const int8_t *act;          /* device [B*m], from mpcqp_adjoint_tape */
+  const int32_t *taped;       /* device [B] */
+} mpcqp_adjoint_point;
+int mpcqp_adjoint_tape(mpcqp_handle *h, const int32_t *status, int8_t *act, int32_t *taped);
+int mpcqp_adjoint_replay(mpcqp_handle *h, const mpcqp_adjoint_point *pt, const mpcqp_adjoint_in *in,
+                         const mpcqp_adjoint_out *out);
 
 /* Zero-copy access to the handle's own problem-data buffers (device): Ax [B*nnzA], l, u [B*m].
  * A producer kernel (e.g. mpcqp_cl_configure) may rewrite them in place between solves, on the

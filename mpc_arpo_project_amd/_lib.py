@@ -54,6 +54,7 @@ EXPORTED = (
     "mpcqp_check_settings", "mpcqp_set_settings_batched", "mpcqp_update_settings",
     "mpcqp_update_settings_batched", "mpcqp_update_rho", "mpcqp_update_rho_batched",
     "mpcqp_get_settings", "mpcqp_polish", "mpcqp_adjoint", "mpcqp_tangent",
+    "mpcqp_adjoint_tape", "mpcqp_adjoint_replay",
     "mpcqp_cl_create", "mpcqp_cl_destroy", "mpcqp_cl_configure", "mpcqp_cl_step",
     "mpcqp_cl_set_ids", "mpcqp_cl_set_tracking", "mpcqp_cl_noise", "mpcqp_cl_set_plant", "mpcqp_clc_period",
     "mpcqp_clc_set_tracking",
@@ -66,7 +67,7 @@ PREDATED = (
     "mpcqp_get_scaling", "mpcqp_check_settings", "mpcqp_set_settings_batched",
     "mpcqp_update_settings", "mpcqp_update_settings_batched", "mpcqp_update_rho",
     "mpcqp_update_rho_batched", "mpcqp_get_settings", "mpcqp_polish", "mpcqp_adjoint",
-    "mpcqp_tangent",
+    "mpcqp_tangent", "mpcqp_adjoint_tape", "mpcqp_adjoint_replay",
 )
 
 STATUS = {
@@ -119,6 +120,12 @@ class AdjointOut(C.Structure):
     _fields_ = [("gq", C.c_void_p), ("gl", C.c_void_p), ("gu", C.c_void_p), ("gPx", C.c_void_p),
                 ("gAx", C.c_void_p), ("res", C.c_void_p), ("act", C.c_void_p),
                 ("status_adjoint", C.c_void_p)]
+
+
+class AdjointPoint(C.Structure):
+    _fields_ = [("Px", C.c_void_p), ("q", C.c_void_p), ("Px_batched", C.c_int32),
+                ("q_batched", C.c_int32), ("Ax", C.c_void_p), ("l", C.c_void_p), ("u", C.c_void_p),
+                ("x", C.c_void_p), ("y", C.c_void_p), ("act", C.c_void_p), ("taped", C.c_void_p)]
 
 
 class TangentIn(C.Structure):
@@ -212,6 +219,9 @@ def lib():
     _sig(L, "mpcqp_polish", "argtypes", [vp, dp, dp, dp, C.POINTER(PolishInfo)])
     _sig(L, "mpcqp_adjoint", "argtypes", [vp, dp, dp, dp, C.POINTER(AdjointIn), C.POINTER(AdjointOut)])
     _sig(L, "mpcqp_tangent", "argtypes", [vp, dp, dp, dp, C.POINTER(TangentIn), C.POINTER(TangentOut)])
+    _sig(L, "mpcqp_adjoint_tape", "argtypes", [vp, dp, dp, dp])
+    _sig(L, "mpcqp_adjoint_replay", "argtypes", [vp, C.POINTER(AdjointPoint), C.POINTER(AdjointIn),
+                                                 C.POINTER(AdjointOut)])
     _sig(L, "mpcqp_dims", "argtypes", [vp, i32p, i32p, i32p, i32p, i32p])
     _sig(L, "mpcqp_engine_kind", "argtypes", [vp, i32p])
     _sig(L, "mpcqp_schedule_kind", "argtypes", [vp, i32p])

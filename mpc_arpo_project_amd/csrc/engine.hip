@@ -2492,6 +2492,7 @@ constexpr int PAIR_PIPE = MPCQP_PAIR_PIPE;
 #include "engine_polish.inc"
 #include "engine_adjoint.inc"
 #include "engine_tangent.inc"
+#include "engine_replay.inc"
 
 // dst[b][k] = src[k] for every instance b (the drift buffers' start: set_data, update_lin_cost)
 __global__ void bcast_rows_kernel(double* dst, const double* src, int B, int cnt) {
@@ -2680,6 +2681,12 @@ struct mpcqp_handle {
   tangent_fn tkern = nullptr;
   int tgrid = 0;
   double* tscratch = nullptr;
+  // adjoint replays (mpcqp_adjoint_replay): legal in every state of the handle, which lends the
+  // plan, the settings rows, the stream and these; the kernel, its grid and its scratch rows, set up
+  // at the first call
+  replay_fn rkern = nullptr;
+  int rgrid = 0;
+  double* rscratch = nullptr;
 };
 
 // device memory owned by the handle: recorded, and freed by mpcqp_destroy
@@ -3304,6 +3311,83 @@ int mpcqp_tangent(mpcqp_handle* h, const int32_t* status, const double* x, const
   tp.status = status, tp.x = x, tp.y = y;
   tp.in = *in, tp.out = *out;
   hipLaunchKernelGGL(h->tkern, dim3(h->tgrid), dim3(64), h->dp.inst_doubles * 8, h->stream, tp);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int mpcqp_adjoint_tape(mpcqp_handle* h, const int32_t* status, int8_t* act, int32_t* taped) {
+  if (!h) return set_error(MPCQP_E_INVALID, "mpcqp_adjoint_tape: null handle");
+  if (!status || !act || !taped) return set_error(MPCQP_E_INVALID, "mpcqp_adjoint_tape: null argument");
+  if (!h->adjoint_ok)
+    return set_error(MPCQP_E_INVALID,
+                     "mpcqp_adjoint_tape: the handle's carried state is not that of its last solve");
+  HIPCHK(launch_1d(h, adjoint_tape_kernel, (size_t)h->B * h->plan.m, h->zs, h->ys, h->Ecls, h->l, h->u, status,
+                   h->skip, h->has_state, h->dsel, act, taped, h->B, h->plan.m));
+  return 0;
+}
+
+// The replay kernel of the handle's plan, its persistent grid and a scratch row per wave (the
+// polish's row: the slab and the sink of the equilibration), as adjoint_setup: at the first
+// mpcqp_adjoint_replay
+static int replay_setup(mpcqp_handle* h) {
+  const Plan& pl = h->plan;
+  const replay_fn k = select_replay(pl.n, pl.m, pl.paired);
+  if (!k)
+    return set_error(MPCQP_E_UNSUPPORTED, "mpcqp_adjoint_replay: problem dimensions exceed the instantiated kernels");
+  int dev = 0, ncu = 0, nb = 0;
+  HIPCHK(hipGetDevice(&dev));
+  HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+  HIPCHK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  hipFuncAttributes fa{};
+  HIPCHK(hipFuncGetAttributes(&fa, (const void*)k));
+  if (fa.numRegs > diag_env_int("MPCQP_REG_BUDGET", MPCQP_MAX_KERNEL_REGS) ||
+      (int)fa.localSizeBytes > MPCQP_MAX_KERNEL_SCRATCH)
+    return set_error(MPCQP_E_UNSUPPORTED,
+                     "mpcqp_adjoint_replay: replay kernel allocates " + std::to_string(fa.numRegs) + " registers / " +
+                         std::to_string(fa.localSizeBytes) + " scratch bytes per lane: above the validated budget");
+  const int lds = h->dp.inst_doubles * 8;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k, 64, lds) != hipSuccess || nb <= 0)
+    return set_error(MPCQP_E_UNSUPPORTED, "mpcqp_adjoint_replay: kernel does not fit on a CU (LDS/VGPR)");
+  const int grid = std::min(h->B, nb * ncu);
+  if (!dev_alloc(h, h->rscratch,
+                 sizeof(double) * (size_t)grid * polish_row_doubles(pl.n, pl.m, pl.mv_slab, pl.nnzP)))
+    return set_error(MPCQP_E_HIP, "mpcqp_adjoint_replay: hipMalloc(scratch rows)");
+  h->rgrid = grid;
+  h->rkern = k;
+  return 0;
+}
+
+int mpcqp_adjoint_replay(mpcqp_handle* h, const mpcqp_adjoint_point* pt, const mpcqp_adjoint_in* in,
+                         const mpcqp_adjoint_out* out) {
+  if (!h) return set_error(MPCQP_E_INVALID, "mpcqp_adjoint_replay: null handle");
+  if (!pt || !in || !out || !in->gx || !pt->Px || !pt->q || !pt->Ax || !pt->l || !pt->u || !pt->x || !pt->y ||
+      !pt->act || !pt->taped)
+    return set_error(MPCQP_E_INVALID, "mpcqp_adjoint_replay: null argument");
+  if (in->nrhs < 1 || in->nrhs > 8)
+    return set_error(MPCQP_E_INVALID, "mpcqp_adjoint_replay: nrhs must be 1..8, got " + std::to_string(in->nrhs));
+  if (in->refine < 0) return set_error(MPCQP_E_INVALID, "mpcqp_adjoint_replay: refine must not be negative");
+  for (size_t i = 0; i < std::max<size_t>(h->rows.size(), 1); ++i)
+    if (!((h->rows.empty() ? h->set : h->rows[i]).delta > 0))
+      return set_error(MPCQP_E_INVALID,
+                       "mpcqp_adjoint_replay: row " + std::to_string(i) + ": delta must be positive");
+  if (!h->rkern)
+    if (int rc = replay_setup(h)) return rc;
+  // the plan, the settings rows and a scratch row per wave are the handle's; the data are the
+  // caller's and no carried array is passed (the zero-initialised members stay null)
+  const Plan& pl = h->plan;
+  RParams rp{};
+  rp.k.pl = h->dp;
+  rp.k.srows = h->rows.empty() ? h->d_set : h->d_rows;
+  rp.k.sstride = h->rows.empty() ? 0 : (int)sizeof(mpcqp_settings);
+  rp.k.B = h->B;
+  rp.k.Px = pt->Px, rp.k.q = pt->q;
+  rp.k.Px_stride = pt->Px_batched ? pl.nnzP : 0, rp.k.q_stride = pt->q_batched ? pl.n : 0;
+  rp.k.Ax = pt->Ax, rp.k.l = pt->l, rp.k.u = pt->u;
+  rp.k.scratch = h->rscratch;
+  rp.k.timing = h->timing;
+  rp.x = pt->x, rp.y = pt->y, rp.act = pt->act, rp.taped = pt->taped;
+  rp.in = *in, rp.out = *out;
+  hipLaunchKernelGGL(h->rkern, dim3(h->rgrid), dim3(64), h->dp.inst_doubles * 8, h->stream, rp);
   HIPCHK(hipGetLastError());
   return 0;
 }

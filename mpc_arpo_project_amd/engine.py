@@ -99,6 +99,23 @@ class TangentResult:
     status_tangent: torch.Tensor  # [B] int32: 1 done, 0 not attempted
 
 
+@dataclass
+class AdjointTape:
+    """What BatchQP.adjoint_replay needs of one solve, taken by BatchQP.tape right after it.  The
+    caller owns it; the handle may solve, update and be re-set-up freely afterwards.  Px and q are
+    references to the cost tensors in force at the solve (shared 1-D or per instance 2-D), not
+    copies: do not write them in place while the tape is in use."""
+    x: torch.Tensor      # [B, n] the unscaled solution (clone)
+    y: torch.Tensor      # [B, m]
+    act: torch.Tensor    # [B, m] int8: -1 lower-active, +1 upper-active, 0 inactive
+    taped: torch.Tensor  # [B] int32: 1 where BatchQP.adjoint would attempt the instance
+    Ax: torch.Tensor     # [B, nnzA] the handle's data at the solve (copies)
+    l: torch.Tensor      # [B, m]
+    u: torch.Tensor
+    Px: torch.Tensor     # [nnzP] or [B, nnzP]
+    q: torch.Tensor      # [n] or [B, n]
+
+
 class BatchQP:
     """B OSQP problems with a shared pattern, solved together on one GPU."""
 
@@ -194,6 +211,7 @@ class BatchQP:
             check(_lib.lib().mpcqp_set_data(self._h, Px.data_ptr(), q.data_ptr(), Ax.data_ptr(),
                                             l.data_ptr(), u.data_ptr()), "mpcqp_set_data")
         self._keep(Px=Px, q=q, Ax=Ax, l=l, u=u)
+        self._cost_now = dict(Px=Px.detach(), q=q.detach())  # the cost data in force (tape)
         self._has_data = True
 
     def update(self, q=None, l=None, u=None, Ax=None, Px=None):
@@ -232,6 +250,9 @@ class BatchQP:
             check(_lib.lib().mpcqp_update_A(self._h, Ax.data_ptr()), "mpcqp_update_A")
             keep["Ax"] = Ax
         self._keep(**keep)
+        for k in ("Px", "q"):
+            if k in keep:
+                self._cost_now[k] = keep[k].detach()
 
     # set-up settings: fixed by the scaling and the factorization set-up, not updatable (OSQP's too)
     SETUP_SETTINGS = ("sigma", "scaling", "adaptive_rho", "adaptive_rho_interval",
@@ -465,6 +486,14 @@ class BatchQP:
         if st.dtype != torch.int32 or tuple(st.shape) != (self.B,) or not st.is_cuda or \
                 not st.is_contiguous():
             raise ValueError(f"status must be a contiguous int32 device tensor of shape ({self.B},)")
+        gx, gy, r, ain, aout = self._adjoint_io(gx, gy, refine, want)
+        check(_lib.lib().mpcqp_adjoint(self._h, st.data_ptr(), o.x.data_ptr(), o.y.data_ptr(),
+                                       C.byref(ain), C.byref(aout)), "mpcqp_adjoint")
+        return self._adjoint_done(gx, gy, r, sync)
+
+    def _adjoint_io(self, gx, gy, refine, want):
+        """the right-hand sides checked and made contiguous, the AdjointResult allocated on the
+        handle's stream, and the two ABI structs of mpcqp_adjoint / mpcqp_adjoint_replay"""
         unknown = [w for w in want if w not in self.ADJOINT_OUTPUTS]
         if unknown:
             raise ValueError(f"unknown adjoint outputs {unknown}: choose from {self.ADJOINT_OUTPUTS}")
@@ -493,8 +522,9 @@ class BatchQP:
         ain = _lib.AdjointIn(nrhs, int(refine), gx.data_ptr(), ptr(gy))
         aout = _lib.AdjointOut(*(ptr(g[k]) for k in self.ADJOINT_OUTPUTS), r.res.data_ptr(),
                                r.act.data_ptr(), r.status_adjoint.data_ptr())
-        check(_lib.lib().mpcqp_adjoint(self._h, st.data_ptr(), o.x.data_ptr(), o.y.data_ptr(),
-                                       C.byref(ain), C.byref(aout)), "mpcqp_adjoint")
+        return gx, gy, r, ain, aout
+
+    def _adjoint_done(self, gx, gy, r, sync):
         for t in (gx, gy):
             if t is not None:
                 t.record_stream(self.stream)
@@ -503,6 +533,69 @@ class BatchQP:
         else:
             torch.cuda.current_stream(self.device).wait_stream(self.stream)
         return r
+
+    def tape(self, out: SolveResult = None, status=None) -> AdjointTape:
+        """Record the last solve for a later adjoint (mpcqp_adjoint_tape), right after solve() or
+        polish(): clones of out's x / y (default: the last result), the active rows and the
+        attempted instances as BatchQP.adjoint would report them at this point (status defaults to
+        out.status), copies of the handle's Ax, l, u, and references to the Px / q tensors in
+        force.  Valid where adjoint is; changes no state.  The caller owns the memory: about
+        (n + 3 m + nnzA) * 8 + m bytes per instance and tape."""
+        o = out if out is not None else getattr(self, "_last", None)
+        if o is None:
+            raise MPCQPError("mpcqp_adjoint_tape: tape before any solve")
+        st = o.status if status is None else status
+        if st.dtype != torch.int32 or tuple(st.shape) != (self.B,) or not st.is_cuda or \
+                not st.is_contiguous():
+            raise ValueError(f"status must be a contiguous int32 device tensor of shape ({self.B},)")
+        f = dict(dtype=torch.float64, device=self.device)
+        Ax = torch.empty(self.B, self.nnzA, **f)
+        l, u = torch.empty(self.B, self.m, **f), torch.empty(self.B, self.m, **f)
+        act = torch.empty(self.B, self.m, dtype=torch.int8, device=self.device)
+        taped = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        x, y = torch.empty_like(o.x), torch.empty_like(o.y)
+
+        def record():
+            check(_lib.lib().mpcqp_adjoint_tape(self._h, st.data_ptr(), act.data_ptr(),
+                                                taped.data_ptr()), "mpcqp_adjoint_tape")
+            check(_lib.lib().mpcqp_copy_data(self._h, Ax.data_ptr(), l.data_ptr(), u.data_ptr()),
+                  "mpcqp_copy_data")
+            with torch.cuda.stream(self.stream):
+                x.copy_(o.x), y.copy_(o.y)
+        self._on_stream(record, Ax, l, u, act, taped, x, y)
+        return AdjointTape(x=x, y=y, act=act, taped=taped, Ax=Ax, l=l, u=u, **self._cost_now)
+
+    def adjoint_replay(self, tape: AdjointTape, gx, gy=None, refine=3, want=("gq", "gl", "gu"),
+                       sync=True) -> AdjointResult:
+        """BatchQP.adjoint of the solve `tape` was taken at, from the tape alone
+        (mpcqp_adjoint_replay): the handle lends its plan, settings and stream and may be in any
+        state -- solved again, updated, given other data, or fresh before set_data (a tape of
+        another handle with the same structure and batch is as good).  gx, gy, refine, want and the
+        result are adjoint's; act echoes the tape's, status_adjoint its `taped`.  Equal to adjoint
+        at the tape point to rounding (bitwise where that solve's scaling started from the
+        set-up data); changes no state."""
+        gx, gy, r, ain, aout = self._adjoint_io(gx, gy, refine, want)
+        pt = self._tape_point(tape)
+        check(_lib.lib().mpcqp_adjoint_replay(self._h, C.byref(pt), C.byref(ain), C.byref(aout)),
+              "mpcqp_adjoint_replay")
+        for t in vars(tape).values():
+            t.record_stream(self.stream)
+        return self._adjoint_done(gx, gy, r, sync)
+
+    def _tape_point(self, tape: AdjointTape):
+        """the ABI's mpcqp_adjoint_point of a tape whose tensors fit this handle"""
+        bP, bq = tape.Px.dim() == 2, tape.q.dim() == 2
+        for t, shape, name in ((tape.Px, (self.B,) * bP + (self.nnzP,), "Px"), (tape.q, (self.B,) * bq + (self.n,), "q"),
+                               (tape.Ax, (self.B, self.nnzA), "Ax"), (tape.l, (self.B, self.m), "l"),
+                               (tape.u, (self.B, self.m), "u"), (tape.x, (self.B, self.n), "x"),
+                               (tape.y, (self.B, self.m), "y"), (tape.act, (self.B, self.m), "act"),
+                               (tape.taped, (self.B,), "taped")):
+            if tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"tape.{name} must be a contiguous device tensor of shape {shape}")
+        return _lib.AdjointPoint(tape.Px.data_ptr(), tape.q.data_ptr(), int(bP), int(bq),
+                                 tape.Ax.data_ptr(), tape.l.data_ptr(), tape.u.data_ptr(),
+                                 tape.x.data_ptr(), tape.y.data_ptr(), tape.act.data_ptr(),
+                                 tape.taped.data_ptr())
 
     TANGENT_OUTPUTS = ("dx", "dy", "dz", "dobj")
 
